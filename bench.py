@@ -24,10 +24,18 @@ runs the same two in-place all-gathers per step as the 8-GPU run (``parallel/dp.
 
 Nothing is cached between steps (the frequency state evolves exactly as the reference's would).
 Rank 0 prints one JSON line; ``value`` is total lines/s over all ranks (max step time across
-ranks). The reference publishes no number, so ``vs_baseline`` is null. After the
-timed loop rank 0 measures p50/p99 of ``POST /parse`` (10k-line body) through a real server
-process started before this process touched the GPU (``p50_parse_ms``), and the engine-only
-latency of the same request (``p50_engine_ms``).
+ranks). The reference publishes no number, so ``vs_baseline`` is null.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line. ``--dump-outputs DIR``
+also writes what the last timed step returned to its caller (global histograms, frequency counts,
+merged top-k rows, and every rank's event records as they arrived in pinned host memory) as
+``DIR/<name>.npy`` in float64; the inputs are seeded, so two builds run with the same arguments
+can be compared array for array.
+
+``--full`` adds the measurements that take runs of their own: each rank's untimed whole-shard
+H2D bandwidth probe, and after the timed loop rank 0's p50/p99 of ``POST /parse`` (10k-line body)
+through a real server process started before this process touched the GPU (``p50_parse_ms``)
+with the engine-only latency of the same request (``p50_engine_ms``).
 """
 from __future__ import annotations
 
@@ -47,6 +55,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-rank H2D bandwidth probe and "
+                         "the /parse latency measurement (--parse-requests, --http, --server-env)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--lines-per-gpu", type=int, default=12_500_000)
     ap.add_argument("--patterns", type=int, default=1000)
     ap.add_argument("--library", default="realistic", choices=["realistic", "synthetic"],
@@ -61,7 +74,8 @@ def parse():
     ap.add_argument("--profile", action="store_true", help="per-stage HIP-event timings (no extra syncs)")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--parse-requests", type=int, default=300,
-                    help="rank 0: p50 latency of N single 10k-line POST /parse requests after the timed loop (0 = off)")
+                    help="--full, rank 0: p50 latency of N single 10k-line POST /parse requests after the timed "
+                         "loop (0 = off)")
     ap.add_argument("--http", default="native", choices=["native", "uvicorn"], help="server front end for p50")
     ap.add_argument("--server-env", action="append", default=[], metavar="KEY=VALUE",
                     help="extra environment of the /parse server process only (A/B knob, repeatable)")
@@ -155,6 +169,41 @@ def _digest(out, top) -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_MAX_EVENTS = 2_000_000          # 3 float64 arrays of this many rows = 48 MB
+
+
+def dump_outputs(path, rank, out, top, ev_host, ev_last):
+    """``--dump-outputs``: what the last timed step handed its caller, as float64 ``.npy`` files
+    (every value is an int64 count / line number below 2^53 or already a double, so float64 is
+    exact). Rank 0 writes the global results: ``pattern_counts``, ``severity_counts``,
+    ``freq_counts`` and ``topk_rows`` (k x [score, global line, pattern], padding rows -inf / -1).
+    Every rank writes its own event records as they landed in pinned host memory:
+    ``events_rank<r>_line`` / ``_score`` / ``_pattern``; above DUMP_MAX_EVENTS events a fixed
+    seeded sample of them (in order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    if rank == 0:
+        for name in ("pattern_counts", "severity_counts", "freq_counts"):
+            t = getattr(out, name)
+            if t is not None:
+                save(name, t.detach().cpu().numpy())
+        if top is not None:
+            save("topk_rows", top.numpy())
+    slot, n = ev_last
+    pk = ev_host[slot][:20 * n].numpy()      # [global line i64 x n | score f64 x n | pattern i32 x n]
+    line, score, pat = pk[:8 * n].view(np.int64), pk[8 * n:16 * n].view(np.float64), pk[16 * n:].view(np.int32)
+    if n > DUMP_MAX_EVENTS:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_EVENTS, replace=False))
+        line, score, pat = line[keep], score[keep], pat[keep]
+    save(f"events_rank{rank}_line", line)
+    save(f"events_rank{rank}_score", score)
+    save(f"events_rank{rank}_pattern", pat)
+
+
 def main():
     args = parse()
     from log_parser_amd.utils import launch
@@ -180,9 +229,9 @@ def main():
     blocks = make_blocks(args, trig)
     hb.phase("blocks")
 
-    # p50 /parse server: started BEFORE this process makes any GPU call (rank 0 only)
+    # --full, p50 /parse server: started BEFORE this process makes any GPU call (rank 0 only)
     server = None
-    if rank == 0 and args.parse_requests > 0:
+    if args.full and rank == 0 and args.parse_requests > 0:
         from log_parser_amd.utils import restbench
         dev = "cpu" if args.device == "cpu" else f"cuda:{local_rank}"
         server = restbench.ServerProcess(restbench.write_library(sets), dev, http=args.http,
@@ -306,7 +355,7 @@ def run(args, sets, trig, blocks, rank, world, local_rank, server, hw_queues=0, 
     ready = [torch.cuda.Event() for _ in range(2)] if use_cuda else None
     free = [torch.cuda.Event() for _ in range(2)] if use_cuda else None
     freed = [False, False]
-    state = {"i": 0, "issued": -1, "events_host": 0}
+    state = {"i": 0, "issued": -1, "events_host": 0, "ev_last": (0, 0)}
     # event records land here (pinned, 2 slots so step k+1's copy never waits on step k's)
     ev_host = [torch.empty(0, dtype=torch.uint8, pin_memory=use_cuda) for _ in range(2)]
 
@@ -327,6 +376,7 @@ def run(args, sets, trig, blocks, rank, world, local_rank, server, hw_queues=0, 
         The D2H runs on the copy stream, behind the prefetch H2D: on the compute stream it would
         queue behind the 23 ms PCIe ingest of the next step and stall the next step's kernels."""
         n = out.result.ev_line.numel()
+        state["ev_last"] = (slot, n)
         if n == 0:
             return
         pk = out.events_packed                  # packed by the summary kernel: [line i64 | score f64 | pat i32]
@@ -386,10 +436,10 @@ def run(args, sets, trig, blocks, rank, world, local_rank, server, hw_queues=0, 
         if use_cuda:
             torch.cuda.synchronize()
 
-    # per-rank diagnostics: this rank's pinned-host -> HBM bandwidth (one whole-shard copy, untimed)
-    # and its GPU's NUMA node, so an 8-GPU result explains itself (a slow socket, a far buffer)
+    # per-rank diagnostics: this rank's pinned-host -> HBM bandwidth (--full: one whole-shard copy,
+    # untimed) and its GPU's NUMA node, so an 8-GPU result explains itself (a slow socket, a far buffer)
     h2d_gbps = 0.0
-    if use_cuda:
+    if use_cuda and args.full:
         a_, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a_.record()
         bufs[0].copy_(host, non_blocking=True)
@@ -432,6 +482,9 @@ def run(args, sets, trig, blocks, rank, world, local_rank, server, hw_queues=0, 
     per_rank = [x[0] for x in per_rank_diag]
     dt = max(per_rank)
     total_lines = last.total_lines
+    if args.dump_outputs:
+        hb.phase("dump outputs")
+        dump_outputs(args.dump_outputs, rank, last, state.get("top"), ev_host, state["ev_last"])
     ms = dt / args.steps * 1e3
     value = total_lines * args.steps / dt
     if rank == 0:
@@ -455,7 +508,8 @@ def run(args, sets, trig, blocks, rank, world, local_rank, server, hw_queues=0, 
             "world_size": dist.get_world_size() if dist.is_initialized() else 1,
             "backend": dist.get_backend() if dist.is_initialized() else "none",
             "ms_per_step_per_rank": [round(x / args.steps * 1e3, 3) for x in per_rank],
-            "per_rank": [{"rank": r, "ms_per_step": round(x[0] / args.steps * 1e3, 3), "h2d_GBps": round(x[1], 2),
+            "per_rank": [{"rank": r, "ms_per_step": round(x[0] / args.steps * 1e3, 3),
+                          "h2d_GBps": round(x[1], 2) if args.full else None,
                           "device_ms": round(x[2], 3), "numa_node": int(x[3])} for r, x in enumerate(per_rank_diag)],
             "collectives_per_step": 2 if dist.is_initialized() else 0,
             "hip_hw_queues": hw_queues,
@@ -478,7 +532,7 @@ def run(args, sets, trig, blocks, rank, world, local_rank, server, hw_queues=0, 
             rec["device_resident_lines_per_s"] = round(own_lines * world / (dms / 1e3), 1)
         if args.profile:
             rec["timings_ms_last_step_rank0"] = {k: round(v, 3) for k, v in TR.resolve(last.result.timings).items()}
-        if args.parse_requests > 0:
+        if args.full and args.parse_requests > 0:
             hb.phase("parse latency")
             # second half of the BASELINE metric: one 10k-line /parse request, same library
             req = make_log(10_000, trig, seed=13, hit_rate=0.01)

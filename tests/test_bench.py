@@ -85,10 +85,11 @@ def test_bench_eight_ranks_cpu(tmp_path):
 
 
 def test_bench_single_rank_parse_over_http(tmp_path):
-    """--gpus 1 --backend gloo on CPU: a process group at world size 1 (collectives still run) and
-    p50 measured through a real POST /parse server process next to the engine-only latency."""
+    """--gpus 1 --backend gloo on CPU: a process group at world size 1 (collectives still run) and,
+    with --full, p50 measured through a real POST /parse server process next to the engine-only
+    latency."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--steps", "1", "--warmup", "1",
-           "--backend", "gloo",
+           "--backend", "gloo", "--full",
            "--lines-per-gpu", "4000", "--block-lines", "4000", "--parse-requests", "2", "--patterns", "60"]
     env = dict(os.environ, OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
@@ -99,6 +100,40 @@ def test_bench_single_rank_parse_over_http(tmp_path):
     assert d["n_gpus"] == 1 and d["world_size"] == 1 and d["backend"] == "gloo"
     assert d["p50_parse_ms"] > 0 and d["p50_engine_ms"] > 0
     assert "HTTP" in d["parse_transport"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) starts no /parse server and measures no request latency or H2D
+    bandwidth, yet reports the headline fields; --dump-outputs writes the last timed step's results
+    as float64 .npy files that agree with the JSON line and with each other."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu", "--steps", "2",
+           "--warmup", "1", "--lines-per-gpu", "4000", "--block-lines", "4000", "--patterns", "60", "--topk", "10",
+           "--dump-outputs", str(dump)]
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert not [k for k in d if k.startswith(("p50_", "p99_", "parse_"))]
+    assert "parse_request_lines" not in d["config"] and d["per_rank"][0]["h2d_GBps"] is None
+    a = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert set(a) == {"pattern_counts", "severity_counts", "freq_counts", "topk_rows",
+                      "events_rank0_line", "events_rank0_score", "events_rank0_pattern"}
+    assert all(v.dtype == np.float64 for v in a.values())
+    n = d["config"]["events_per_step"]
+    assert n > 0 and a["pattern_counts"].sum() == n == a["severity_counts"].sum()
+    assert len(a["events_rank0_line"]) == len(a["events_rank0_score"]) == len(a["events_rank0_pattern"]) == n
+    assert np.array_equal(np.bincount(a["events_rank0_pattern"].astype(np.int64),
+                                      minlength=len(a["pattern_counts"])), a["pattern_counts"])
+    assert a["topk_rows"].shape == (10, 3)
+    k = int(np.isfinite(a["topk_rows"][:, 0]).sum())
+    assert k == min(10, n) and np.array_equal(a["topk_rows"][:k, 0], np.sort(a["events_rank0_score"])[::-1][:k])
 
 
 def test_bench_hang_guard_reports_phases(tmp_path):

@@ -588,6 +588,13 @@ def test_burst_mode_bodies_reach_the_packer_undecoded():
               for i, l in enumerate(logs)]
     assert len(bodies[-1]) >= 64 << 10
     outs = {}
+
+    def paced(b):       # as _conn_send(slow=True): the body arrives over several reads, on any machine
+        import time
+        for i in range(0, len(b), 8191):
+            yield b[i:i + 8191]
+            time.sleep(0.0005)
+
     for limit in (-1, 0):
         lib = CompiledLibrary(sets, ScoringParams())
         cfg = Config.load(overrides={"engine.device": "cpu", "server.max-body-bytes": 4 << 20,
@@ -598,7 +605,7 @@ def test_burst_mode_bodies_reach_the_packer_undecoded():
             c = http.client.HTTPConnection("127.0.0.1", fe.port, timeout=60)
             res = []
             for b in bodies:
-                st, out = _post(c, b)
+                st, out = _post(c, paced(b), {"content-length": str(len(b))})
                 assert st == 200
                 res.append(_strip(json.loads(out)))
             c.close()

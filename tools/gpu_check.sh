@@ -120,7 +120,7 @@ for s in $steps; do
     full)
       run full_pytest 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
       run full_smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-      run full_bench 300 python -u bench.py ;;
+      run full_bench 300 python -u bench.py --full ;;
     singletrace)
       cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
       run single_prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_single -o run -- \

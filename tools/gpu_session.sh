@@ -13,5 +13,5 @@ run() {   # run NAME SECONDS CMD... : stop the session at the first failure
 }
 
 run ps1 300 python -u tools/parse_stages.py --n 400
-run bench 400 python -u bench.py
+run bench 400 python -u bench.py --full
 run ps2 300 python -u tools/parse_stages.py --n 400
