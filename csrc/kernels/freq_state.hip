@@ -17,6 +17,7 @@
 #include <string>
 
 #include "lp_api.h"
+#include "post_core.h"
 
 namespace lp {
 
@@ -44,17 +45,8 @@ __global__ __launch_bounds__(256) void k_freq_record(const int64_t* __restrict__
                                                      FreqRing R, RecordGate G) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
-  if (G.cnt && (G.cnt[0] > G.cap[0] || G.cnt[1] > G.cap[1] || G.cnt[2] > G.cap[2] || G.cnt[4] > G.cap[3])) return;
-  if (G.veto && *G.veto) return;
-  const int64_t c = counts[k];
-  if (c <= 0) return;
-  const int64_t p = (int64_t)atomicAdd(reinterpret_cast<unsigned long long*>(R.ht + 1), 1ull);
-  const int64_t s = p % R.cap;                // capacity is guaranteed by the host (grow before)
-  R.t[s] = now;
-  R.key[s] = k;
-  R.cnt[s] = (int32_t)c;
-  R.tot[k] += c;                              // one thread per key: no race
-  R.seen[k] = 1;
+  if (!record_gate_open(G)) return;
+  freq_record_key(R, k, counts[k], now);
 }
 
 void freq_evict(const FreqRing& R, double horizon, uint64_t stream, bool dev) {
@@ -84,16 +76,7 @@ void freq_record(const int64_t* counts, int K, double now, const FreqRing& R, ui
     return;
   }
   if (gate.veto && *gate.veto) return;
-  for (int k = 0; k < K; ++k) {
-    const int64_t c = counts[k];
-    if (c <= 0) continue;
-    const int64_t s = R.ht[1]++ % R.cap;
-    R.t[s] = now;
-    R.key[s] = k;
-    R.cnt[s] = (int32_t)c;
-    R.tot[k] += c;
-    R.seen[k] = 1;
-  }
+  for (int k = 0; k < K; ++k) freq_record_key(R, k, counts[k], now);
 }
 
 }  // namespace lp

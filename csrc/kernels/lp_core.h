@@ -592,6 +592,40 @@ LP_HD double pen_factor(const ScoreParams& S, int64_t freq_before) {
   return pen;
 }
 
+// an event's own factors and THE product of a score (left to right, on every backend)
+struct ScoreOwn {
+  double conf = 0.0, sev = 0.0, chrono = 0.0, pen = 0.0;
+};
+LP_HD double score_product(const ScoreOwn& o, double prox, double temp, double ctx) {
+  return o.conf * o.sev * o.chrono * prox * temp * ctx * (1.0 - o.pen);
+}
+
+// The factors of event e split over four wave-uniform `part`s of a workgroup (k_score, the request
+// tail): proximity, temporal and context are each a chain of dependent table / hit-list loads, so
+// parts 0-2 run them side by side into slot j of their LDS row while part 3 loads the event's own
+// factors (returned). After a barrier part 3 multiplies with score_product, as score_event does.
+LP_HD ScoreOwn score_split(const ScoreTables& T, const ScoreParams& S, const FreqIn& F, const int32_t* ev_line,
+                           const int32_t* ev_pat, const int32_t* ev_seg, int part, int64_t e, bool on, double* fx_prox,
+                           double* fx_temp, double* fx_ctx, int j) {
+  ScoreOwn o;
+  if (!on) return o;
+  const int32_t x = ev_line[e], p = ev_pat[e], sg = ev_seg[e];
+  const int32_t lo = T.seg_lo[sg], hi = T.seg_hi[sg];
+  if (part == 0) {
+    fx_prox[j] = prox_factor(T, S, x, p, lo, hi);
+  } else if (part == 1) {
+    fx_temp[j] = temp_factor(T, x, p, lo, hi, T.seg_own_lo[sg]);
+  } else if (part == 2) {
+    fx_ctx[j] = ctx_factor(T, S, x, p, lo, hi);
+  } else {
+    o.conf = T.conf[p];
+    o.sev = T.sev[p];
+    o.chrono = chrono_factor(T.seg_g0[sg] + (x - lo), T.seg_n[sg], S);
+    o.pen = pen_factor(S, freq_before(F, e));
+  }
+  return o;
+}
+
 LP_HD double score_event(const ScoreTables& T, const ScoreParams& S, int32_t x, int32_t p, int32_t s,
                          int64_t freq_before, double* factors /* optional [7] */) {
   const int32_t lo = T.seg_lo[s], hi = T.seg_hi[s], own_lo = T.seg_own_lo[s];
@@ -607,7 +641,7 @@ LP_HD double score_event(const ScoreTables& T, const ScoreParams& S, int32_t x, 
     factors[0] = conf; factors[1] = sev; factors[2] = chrono; factors[3] = prox;
     factors[4] = temp; factors[5] = ctx; factors[6] = pen;
   }
-  return conf * sev * chrono * prox * temp * ctx * (1.0 - pen);
+  return score_product(ScoreOwn{conf, sev, chrono, pen}, prox, temp, ctx);
 }
 
 }  // namespace lp

@@ -403,31 +403,15 @@ __global__ __launch_bounds__(4 * kScoreEv) void k_score(const int32_t* __restric
   const int part = (int)threadIdx.x / kScoreEv, j = (int)threadIdx.x % kScoreEv;   // part: wave-uniform
   const int64_t i = (int64_t)blockIdx.x * kScoreEv + j;
   const bool on = i < n && !(dn && i >= dn[0]);
-  double conf = 0.0, sev = 0.0, chrono = 0.0, pen = 0.0;
-  if (on) {
-    const int32_t x = ev_line[i], p = ev_pat[i], sg = ev_seg[i];
-    const int32_t lo = T.seg_lo[sg], hi = T.seg_hi[sg];
-    if (part == 0) {
-      fx[0][j] = prox_factor(T, S, x, p, lo, hi);
-    } else if (part == 1) {
-      fx[1][j] = temp_factor(T, x, p, lo, hi, T.seg_own_lo[sg]);
-    } else if (part == 2) {
-      fx[2][j] = ctx_factor(T, S, x, p, lo, hi);
-    } else {
-      conf = T.conf[p];
-      sev = T.sev[p];
-      chrono = chrono_factor(T.seg_g0[sg] + (x - lo), T.seg_n[sg], S);
-      pen = pen_factor(S, freq_before(F, i));
-    }
-  }
+  const ScoreOwn o = score_split(T, S, F, ev_line, ev_pat, ev_seg, part, i, on, fx[0], fx[1], fx[2], j);
   __syncthreads();
   if (part != 3 || !on) return;
   const double prox = fx[0][j], temp = fx[1][j], ctx = fx[2][j];
   if (factors) {
     double* f = factors + 7 * i;
-    f[0] = conf; f[1] = sev; f[2] = chrono; f[3] = prox; f[4] = temp; f[5] = ctx; f[6] = pen;
+    f[0] = o.conf; f[1] = o.sev; f[2] = o.chrono; f[3] = prox; f[4] = temp; f[5] = ctx; f[6] = o.pen;
   }
-  out[i] = conf * sev * chrono * prox * temp * ctx * (1.0 - pen);
+  out[i] = score_product(o, prox, temp, ctx);
 }
 
 

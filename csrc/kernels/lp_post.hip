@@ -663,74 +663,25 @@ __global__ __launch_bounds__(SB_THREADS) void k_request_tail(HitsArgs HA, Events
     const int part = (int)threadIdx.x / SC_EV, i = (int)threadIdx.x % SC_EV;   // part: wave-uniform
     for (int64_t b0 = 0; b0 < ne; b0 += SC_EV) {
       const int64_t e = b0 + i;
-      double conf = 0.0, sev = 0.0, chrono = 0.0, pen = 0.0;
-      if (e < ne) {
-        const int32_t x = EA.ev_line[e], p = EA.ev_pat[e], sg = EA.ev_seg[e];
-        const int32_t lo = T.seg_lo[sg], hi = T.seg_hi[sg];
-        if (part == 0) {
-          fx[i] = prox_factor(T, S, x, p, lo, hi);
-        } else if (part == 1) {
-          fx[SC_EV + i] = temp_factor(T, x, p, lo, hi, T.seg_own_lo[sg]);
-        } else if (part == 2) {
-          fx[2 * SC_EV + i] = ctx_factor(T, S, x, p, lo, hi);
-        } else {
-          conf = T.conf[p];
-          sev = T.sev[p];
-          chrono = chrono_factor(T.seg_g0[sg] + (x - lo), T.seg_n[sg], S);
-          pen = pen_factor(S, freq_before(F, e));
-        }
-      }
+      const ScoreOwn o = score_split(T, S, F, EA.ev_line, EA.ev_pat, EA.ev_seg, part, e, e < ne, fx, fx + SC_EV,
+                                     fx + 2 * SC_EV, i);
       __syncthreads();
-      if (part == 3 && e < ne)
-        P.score[e] = conf * sev * chrono * fx[i] * fx[SC_EV + i] * fx[2 * SC_EV + i] * (1.0 - pen);
+      if (part == 3 && e < ne) P.score[e] = score_product(o, fx[i], fx[SC_EV + i], fx[2 * SC_EV + i]);
       __syncthreads();
     }
   }
   LP_SB_STAMP(6);
   // the frequency record of the batch's per-key counts (penalty before record: after the score),
   // gated on the matcher capacities as k_publish_record / k_freq_record
-  const int64_t* cnt = P.cnt;
-  const RecordGate& G = P.gate;
-  const bool fits = !over && !(G.cnt && (G.cnt[0] > G.cap[0] || G.cnt[1] > G.cap[1] || G.cnt[2] > G.cap[2] ||
-                                         ne > G.cap[3]));
-  if (fits) {
-    const FreqRing& R = P.ring;
-    for (int k = threadIdx.x; k < P.K; k += SB_THREADS) {
-      const int64_t c = P.counts[k];
-      if (c <= 0) continue;
-      const int64_t q = (int64_t)atomicAdd(reinterpret_cast<unsigned long long*>(R.ht + 1), 1ull);
-      const int64_t s = q % R.cap;
-      R.t[s] = P.now;
-      R.key[s] = k;
-      R.cnt[s] = (int32_t)c;
-      R.tot[k] += c;
-      R.seen[k] = 1;
-    }
-  }
+  if (!over && record_gate_open(P.gate, ne))
+    for (int k = threadIdx.x; k < P.K; k += SB_THREADS) freq_record_key(P.ring, k, P.counts[k], P.now);
   LP_SB_STAMP(7);
-  // counters + compacted results into pinned host memory (k_publish_record's layout)
-  if (threadIdx.x < 5) P.cnt_host[threadIdx.x] = threadIdx.x == 3 ? nh : threadIdx.x == 4 ? ne : cnt[threadIdx.x];
-  const int64_t E = P.E;
-  if (over || ne < 0 || ne > E) return;
-  const uint8_t* out = P.out;
-  const double* score = reinterpret_cast<const double*>(out);
-  const int64_t* counts_e = reinterpret_cast<const int64_t*>(out + 8 * E);
-  const int32_t* cols = reinterpret_cast<const int32_t*>(out + 8 * E + 8 * (int64_t)P.K1);
-  double* h_score = reinterpret_cast<double*>(P.res_host);
-  int64_t* h_counts = reinterpret_cast<int64_t*>(P.res_host + 8 * ne);
-  int32_t* h_cols = reinterpret_cast<int32_t*>(P.res_host + 8 * ne + 8 * (int64_t)P.K1);
-  const int64_t total = ne + P.K1 + 3 * ne;
-  for (int64_t i = threadIdx.x; i < total; i += SB_THREADS) {
-    if (i < ne) {
-      h_score[i] = score[i];
-    } else if (i < ne + P.K1) {
-      h_counts[i - ne] = counts_e[i - ne];
-    } else {
-      const int64_t j = i - ne - P.K1;
-      const int64_t c = j / ne, r = j - c * ne;
-      h_cols[j] = cols[c * E + r];
-    }
-  }
+  // counters (hits / events as held here, not re-read) + compacted results into pinned host memory;
+  // over capacity: the counters only
+  const int64_t* cnt = P.cnt;
+  if (!publish_results([&](int64_t c) { return c == 3 ? nh : c == 4 ? ne : cnt[c]; }, P.out, P.E, P.K1, over ? -1 : ne,
+                       P.cnt_host, P.res_host, threadIdx.x, SB_THREADS))
+    return;
   __syncthreads();
   LP_SB_STAMP(15);
 }
@@ -882,13 +833,7 @@ size_t events_dev(const EventsArgs& A, void* ws, size_t ws_bytes, uint64_t strea
     if (!A.cov && (!ws || D.used > ws_bytes)) return D.used;
     hipLaunchKernelGGL(k_events_small, dim3(1), dim3(SB_THREADS), 0, pstream(stream), A, cov_s);
     LP_PCHECK(hipGetLastError());
-    if (L > 0 && A.feat && !A.feat_ready) {
-      int per = (int)std::min<int64_t>(FC_MAX_LINES, std::max<int64_t>(256, L / 1024));
-      per = (per + 255) / 256 * 256;
-      hipLaunchKernelGGL(k_feat_cov, dim3(nblk(L, per)), dim3(256), 0, pstream(stream), cov_s, L, per, A.text, A.ls,
-                         A.ll, A.dfa, A.ctx_trans, A.ctx_acc, A.feat);
-      LP_PCHECK(hipGetLastError());
-    }
+    if (!A.feat_ready) feat_cov_dev(cov_s, L, A.text, A.ls, A.ll, A.dfa, A.ctx_trans, A.ctx_acc, A.feat, stream);
     return D.used;
   }
   if (events_bulk_ok(A)) return events_bulk_dev(A, ws, ws_bytes, stream);   // bucket sorts (post_bulk.hip)
@@ -916,16 +861,7 @@ size_t events_dev(const EventsArgs& A, void* ws, size_t ws_bytes, uint64_t strea
                        A.freq_counts);
     LP_PCHECK(hipGetLastError());
   }
-  if (L > 0) {
-    if (A.feat) {
-      // lines per block: enough blocks to spread a small request over the CUs, 4096 for big ones
-      int per = (int)std::min<int64_t>(FC_MAX_LINES, std::max<int64_t>(256, L / 1024));
-      per = (per + 255) / 256 * 256;
-      hipLaunchKernelGGL(k_feat_cov, dim3(nblk(L, per)), dim3(256), 0, st, cov, L, per, A.text, A.ls, A.ll, A.dfa,
-                         A.ctx_trans, A.ctx_acc, A.feat);
-      LP_PCHECK(hipGetLastError());
-    }
-  }
+  feat_cov_dev(cov, L, A.text, A.ls, A.ll, A.dfa, A.ctx_trans, A.ctx_acc, A.feat, stream);
   return C.used;
 }
 

@@ -1,7 +1,8 @@
 // Element functions of the post-match pipeline (host + device), shared by the per-batch kernels of
 // lp_post.hip, the bucket-sorted bulk path of post_bulk.hip and the host twins: the same arithmetic
 // and ordering rules on every backend (reference semantics: AnalysisService.java:89-156,
-// ScoringService.java:84-88).
+// ScoringService.java:84-88). Also the request's record gate, ring append and results publish, which
+// freq_state.hip, request_io.hip and the single-kernel request tail share.
 #pragma once
 #include <stdint.h>
 
@@ -113,6 +114,62 @@ LP_HD void rank_one(const uint32_t* fs, const int32_t* idx, int64_t ne, int64_t 
   ev_rank[e] = j - start;
   ev_fkey[e] = fk;
   if (j + 1 == ne || fs[j + 1] != fk) freq_counts[fk] = j - start + 1;
+}
+
+// the batch may enter the frequency window: the matcher counters are within their capacities, its
+// `ne` events within cap[3] (so the per-key counts are the batch's real ones) and no veto is set
+LP_HD bool record_gate_open(const RecordGate& G, int64_t ne) {
+  if (G.cnt && (G.cnt[0] > G.cap[0] || G.cnt[1] > G.cap[1] || G.cnt[2] > G.cap[2] || ne > G.cap[3])) return false;
+  return !(G.veto && *G.veto);
+}
+LP_HD bool record_gate_open(const RecordGate& G) { return record_gate_open(G, G.cnt ? G.cnt[4] : 0); }
+
+// the window's ring append of one key's batch count c (freq_state.hip); the device draws the slot's
+// ticket atomically (one lane per key), the host twin in key order. The host guarantees capacity.
+LP_HD void freq_record_key(const FreqRing& R, int k, int64_t c, double now) {
+  if (c <= 0) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int64_t p = (int64_t)atomicAdd(reinterpret_cast<unsigned long long*>(R.ht + 1), 1ull);
+#else
+  const int64_t p = R.ht[1]++;
+#endif
+  const int64_t s = p % R.cap;
+  R.t[s] = now;
+  R.key[s] = k;
+  R.cnt[s] = (int32_t)c;
+  R.tot[k] += c;                              // one lane per key: no race
+  R.seen[k] = 1;
+}
+
+// Device-count-mode results into pinned host memory (request_io.hip has the layout): lane gid of
+// `stride` writes counter(gid) for the 5 counters, then the lanes compact the results `out` (event
+// capacity E) to stride ne. Only the counters when ne is outside [0, E]; returns whether the
+// results went out. counter(i): the request tail holds hits / events in registers.
+template <class Counter>
+LP_HD bool publish_results(Counter counter, const uint8_t* __restrict__ out, int64_t E, int K1, int64_t ne,
+                           int64_t* __restrict__ cnt_host, uint8_t* __restrict__ res_host, int64_t gid,
+                           int64_t stride) {
+  if (gid < 5) cnt_host[gid] = counter(gid);
+  if (ne < 0 || ne > E) return false;
+  const double* score = reinterpret_cast<const double*>(out);
+  const int64_t* counts = reinterpret_cast<const int64_t*>(out + 8 * E);
+  const int32_t* cols = reinterpret_cast<const int32_t*>(out + 8 * E + 8 * (int64_t)K1);
+  double* h_score = reinterpret_cast<double*>(res_host);
+  int64_t* h_counts = reinterpret_cast<int64_t*>(res_host + 8 * ne);
+  int32_t* h_cols = reinterpret_cast<int32_t*>(res_host + 8 * ne + 8 * (int64_t)K1);
+  const int64_t total = ne + K1 + 3 * ne;
+  for (int64_t i = gid; i < total; i += stride) {
+    if (i < ne) {
+      h_score[i] = score[i];
+    } else if (i < ne + K1) {
+      h_counts[i - ne] = counts[i - ne];
+    } else {
+      const int64_t j = i - ne - K1;           // column c = j / ne, row r = j % ne
+      const int64_t c = j / ne, r = j - c * ne;
+      h_cols[j] = cols[c * E + r];
+    }
+  }
+  return true;
 }
 
 // launchers of lp_post.hip kernels reused by the bulk path

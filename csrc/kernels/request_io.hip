@@ -20,65 +20,24 @@
 #include <string>
 
 #include "lp_api.h"
+#include "post_core.h"
 
 namespace lp {
 
 __global__ __launch_bounds__(256) void k_publish(const int64_t* __restrict__ cnt, const uint8_t* __restrict__ out,
                                                  int64_t E, int K1, int64_t* __restrict__ cnt_host,
                                                  uint8_t* __restrict__ res_host) {
-  const int64_t ne = cnt[4];
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (gid < 5) cnt_host[gid] = cnt[gid];
-  if (ne < 0 || ne > E) return;
-  const double* score = reinterpret_cast<const double*>(out);
-  const int64_t* counts = reinterpret_cast<const int64_t*>(out + 8 * E);
-  const int32_t* cols = reinterpret_cast<const int32_t*>(out + 8 * E + 8 * (int64_t)K1);
-  double* h_score = reinterpret_cast<double*>(res_host);
-  int64_t* h_counts = reinterpret_cast<int64_t*>(res_host + 8 * ne);
-  int32_t* h_cols = reinterpret_cast<int32_t*>(res_host + 8 * ne + 8 * (int64_t)K1);
-  const int64_t total = ne + K1 + 3 * ne;
-  for (int64_t i = gid; i < total; i += stride) {
-    if (i < ne) {
-      h_score[i] = score[i];
-    } else if (i < ne + K1) {
-      h_counts[i - ne] = counts[i - ne];
-    } else {
-      const int64_t j = i - ne - K1;           // column c = j / ne, row r = j % ne
-      const int64_t c = j / ne, r = j - c * ne;
-      h_cols[j] = cols[c * E + r];
-    }
-  }
+  publish_results([cnt](int64_t i) { return cnt[i]; }, out, E, K1, cnt[4], cnt_host, res_host,
+                  (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // Inputs of a request from pinned host memory straight into the workspace: one kernel whose
 // lanes each keep up to 4 16-byte PCIe reads in flight. Replaces the SDMA copy, whose completion
 // the compute queue only sees ~9 us later (request trace: copy 32 us + 9.6 us gap before it and
 // 8.9 us after it).
-// With `evict`, block 0 first drops the frequency window's records at or before `horizon` (the
-// request's k_freq_evict, freq_state.hip: it reads nothing the fetch writes) and the fetch runs on
-// the other blocks: one launch fewer per request.
-__global__ __launch_bounds__(256) void k_fetch(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t n,
-                                               int evict, FreqRing R, double horizon) {
-  if (evict && blockIdx.x == 0) {
-    for (;;) {
-      const int64_t head = R.ht[0], tail = R.ht[1];
-      const int64_t i = head + threadIdx.x;
-      bool v = false;
-      if (i < tail) {
-        const int64_t s = i % R.cap;
-        v = R.t[s] <= horizon;
-        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(R.tot + R.key[s]),
-                         (unsigned long long)(-(int64_t)R.cnt[s]));
-      }
-      const int c = __syncthreads_count(v);   // a prefix of the window: timestamps are ordered
-      if (threadIdx.x == 0) R.ht[0] = head + c;
-      __syncthreads();
-      if (c < (int)blockDim.x) return;
-    }
-  }
-  const int64_t stride = (int64_t)(gridDim.x - evict) * blockDim.x;
-  int64_t i = (int64_t)(blockIdx.x - evict) * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void k_fetch(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + 3 * stride < n; i += 4 * stride) {
     const uint4 a = src[i], b = src[i + stride], c = src[i + 2 * stride], d = src[i + 3 * stride];
     dst[i] = a;
@@ -89,13 +48,11 @@ __global__ __launch_bounds__(256) void k_fetch(const uint4* __restrict__ src, ui
   for (; i < n; i += stride) dst[i] = src[i];
 }
 
-void fetch_dev(const void* host_dev, void* dst, int64_t n16, uint64_t stream, const FreqRing* evict, double horizon) {
-  if (n16 <= 0 && !evict) return;
+void fetch_dev(const void* host_dev, void* dst, int64_t n16, uint64_t stream) {
+  if (n16 <= 0) return;
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n16 + 255) / 256));
-  const int ev = evict ? 1 : 0;
-  hipLaunchKernelGGL(k_fetch, dim3(blocks + ev), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     static_cast<const uint4*>(host_dev), static_cast<uint4*>(dst), n16, ev,
-                     evict ? *evict : FreqRing{}, horizon);
+  hipLaunchKernelGGL(k_fetch, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const uint4*>(host_dev), static_cast<uint4*>(dst), n16);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e) + " in fetch");
 }
@@ -111,41 +68,12 @@ __global__ __launch_bounds__(256) void k_publish_record(const int64_t* __restric
   if ((int)blockIdx.x < rec_blocks) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
-    if (G.cnt && (G.cnt[0] > G.cap[0] || G.cnt[1] > G.cap[1] || G.cnt[2] > G.cap[2] || G.cnt[4] > G.cap[3])) return;
-    const int64_t c = counts[k];
-    if (c <= 0) return;
-    const int64_t p = (int64_t)atomicAdd(reinterpret_cast<unsigned long long*>(R.ht + 1), 1ull);
-    const int64_t s = p % R.cap;
-    R.t[s] = now;
-    R.key[s] = k;
-    R.cnt[s] = (int32_t)c;
-    R.tot[k] += c;
-    R.seen[k] = 1;
+    if (record_gate_open(G)) freq_record_key(R, k, counts[k], now);
     return;
   }
-  const int64_t ne = cnt[4];
-  const int64_t gid = (int64_t)(blockIdx.x - rec_blocks) * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)(gridDim.x - rec_blocks) * blockDim.x;
-  if (gid < 5) cnt_host[gid] = cnt[gid];
-  if (ne < 0 || ne > E) return;
-  const double* score = reinterpret_cast<const double*>(out);
-  const int64_t* counts_e = reinterpret_cast<const int64_t*>(out + 8 * E);
-  const int32_t* cols = reinterpret_cast<const int32_t*>(out + 8 * E + 8 * (int64_t)K1);
-  double* h_score = reinterpret_cast<double*>(res_host);
-  int64_t* h_counts = reinterpret_cast<int64_t*>(res_host + 8 * ne);
-  int32_t* h_cols = reinterpret_cast<int32_t*>(res_host + 8 * ne + 8 * (int64_t)K1);
-  const int64_t total = ne + K1 + 3 * ne;
-  for (int64_t i = gid; i < total; i += stride) {
-    if (i < ne) {
-      h_score[i] = score[i];
-    } else if (i < ne + K1) {
-      h_counts[i - ne] = counts_e[i - ne];
-    } else {
-      const int64_t j = i - ne - K1;
-      const int64_t c = j / ne, r = j - c * ne;
-      h_cols[j] = cols[c * E + r];
-    }
-  }
+  publish_results([cnt](int64_t i) { return cnt[i]; }, out, E, K1, cnt[4], cnt_host, res_host,
+                  (int64_t)(blockIdx.x - rec_blocks) * blockDim.x + threadIdx.x,
+                  (int64_t)(gridDim.x - rec_blocks) * blockDim.x);
 }
 
 void publish_record_dev(const int64_t* cnt, const uint8_t* out, int64_t E, int K1, int64_t* cnt_host,

@@ -155,6 +155,27 @@ class RequestRunner {
   int64_t stride() const { return stride_; }
 
  private:
+  // one run(): its arguments, upload layout, window state and the buffers carved from the
+  // workspace (request.cpp); the stages of run() below work on it
+  struct Run;
+  void stage_inputs(Run& r, const int32_t* seg_lo, const int32_t* seg_hi, const int64_t* seg_g0, const int64_t* seg_n,
+                    int64_t host_cap, int64_t pre_token);
+  void size_attempt(Run& r, int attempt) const;   // matcher capacities from the learned rates
+  void carve(Run& r);                  // every buffer of an attempt; sizes (no workspace) or carves
+  void carve_events(Run& r, int64_t E);
+  void upload(Run& r, int attempt);
+  bool run_matchers(Run& r, int attempt);   // returns: the prefilter candidates are verified already
+  void run_tail(Run& r, const HitsArgs& HA);
+  void run_hits(Run& r, const HitsArgs& HA);
+  void run_events(Run& r, int64_t E, int64_t nh_cap, const int64_t* dcnt);
+  void run_score(Run& r, int64_t E, const int64_t* dcnt, const int64_t* tot);
+  void enter_window(Run& r);           // shared window: wait for the earlier batches, then evict
+  void hw_enter(Run& r);               // host window: ticket, host eviction, carry
+  void hw_leave(Run& r);
+  void hw_record(Run& r, int64_t ne);  // host window: the section's record of the compacted results
+  void learn(const RequestCounts& c, const Run& r, bool ok);
+  void ensure_results(size_t bytes);   // pinned results (and their device view) of at least `bytes`
+  void finish_host_counts(Run& r, int64_t nh, int64_t ne);
   uint8_t* dev(size_t bytes);          // carve from the device workspace (grown between runs)
   uint8_t* inj_host_ = nullptr;        // pinned staging of host-verified keys (backtracker side path)
   size_t inj_cap_ = 0;
@@ -172,9 +193,6 @@ class RequestRunner {
   int64_t* cnt_host_ = nullptr;        // pinned counters (fine-grained: k_publish writes them)
   int64_t* cnt_host_dev_ = nullptr;    // ... and the device's address of them
   uint8_t* res_host_dev_ = nullptr;    // device address of res_host_
-  bool publish_ = true;                // device-count mode: results published by k_publish
-  bool fetch_ = true;                  // single-copy inputs read by k_fetch from the pinned stage
-  bool evict_in_fetch_ = false;        // the window eviction runs inside the k_fetch launch (opt-in)
   uint8_t* fetch_host_ = nullptr;      // last stage buffer seen ...
   uint8_t* fetch_dev_ = nullptr;       // ... and its device address (null: not mapped, SDMA copy)
   int64_t fetch_cap_ = 0;
@@ -192,7 +210,6 @@ class RequestRunner {
   // candidate verification (fork after the inputs, join before the hit pipeline)
   hipStream_t side_ = nullptr;
   hipEvent_t fork_ = nullptr, join_ = nullptr;
-  bool side_on_ = true;
 };
 
 }  // namespace lp

@@ -319,3 +319,39 @@ def test_native_runner_fetch_publish_equal_orchestration(gpu_device):
         assert (eng._runner not in (None, False)) == native
     assert outs[True] == outs[False]
     assert sum(len(o["events"]) for b in outs[True] for o in b) > 50
+
+
+def test_native_runner_single_kernel_tail_equals_orchestration(gpu_device):
+    """A library with bit-parallel (BPG) programs lets the runner verify every candidate before the
+    join, so a request's tail runs as the ONE k_request_tail kernel (hits, events, score, gated
+    record, publish). Responses equal the Python orchestration's over batches that include one whose
+    candidates exceed the first capacities (device gate closed, nothing recorded, host-count re-run),
+    and the kernel's last phase stamp (slot 15, written by nothing else) shows it ran."""
+    import json
+    from log_parser_amd.native import N
+    sets, trig = make_library(60, seed=3, java_shape_rate=0.35, gap_rate=0.1)
+    lib = CompiledLibrary(sets, ScoringParams())
+    assert lib.summary()["nfa_bpg"] >= 8
+    batches = [[make_log(n, trig, seed=30 + i, hit_rate=0.12) for i, n in enumerate((900, 1200, 1500))],
+               [make_log(6000, trig, seed=35, hit_rate=0.3)],
+               [make_log(500, trig, seed=36, hit_rate=0.02), "", "\n"]]
+    outs = {}
+    for on in (True, False):
+        cfg = Config.load(overrides={"engine.device": str(gpu_device), "engine.native-runner": on})
+        eng = Engine(lib, cfg, device=gpu_device)
+        outs[on] = []
+        for i, b in enumerate(batches):
+            if on and i == 0:
+                prof = torch.zeros(16, dtype=torch.int64, device=gpu_device)
+                N.set_small_profile(prof.data_ptr())
+                try:
+                    outs[on].append([_strip(json.loads(o)) for o in eng.analyze_batch_json(b)])
+                    torch.cuda.synchronize()
+                finally:
+                    N.set_small_profile(0)
+                assert int(prof[15]) != 0, "k_request_tail did not run"
+            else:
+                outs[on].append([_strip(json.loads(o)) for o in eng.analyze_batch_json(b)])
+        assert (eng._runner not in (None, False)) == on
+    assert outs[True] == outs[False]
+    assert sum(len(o["events"]) for b in outs[True] for o in b) > 50
