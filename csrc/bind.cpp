@@ -1058,6 +1058,38 @@ PYBIND11_MODULE(_lpnative, m) {
                         uint64_t out, int64_t cap) {
     return scan_host(P<const uint8_t>(text), P<const int64_t>(ls), P<const int32_t>(ll), nl, P<const int32_t>(regs),
                      nregs, dfa_from(dfa), P<int64_t>(out), cap); });
+  // ---- coverage-gap report (gaps.hip): context features of every line, template signatures
+  m.def("feat_all_dev", [](int64_t L, uint64_t text, uint64_t ls, uint64_t ll, py::tuple dfa, int ctx_trans,
+                           int ctx_acc, uint64_t feat, uint64_t s) {
+    feat_all_dev(L, P<const uint8_t>(text), P<const int64_t>(ls), P<const int32_t>(ll), dfa_from(dfa), ctx_trans,
+                 ctx_acc, P<uint8_t>(feat), s); },
+        py::arg("L"), py::arg("text"), py::arg("ls"), py::arg("ll"), py::arg("dfa"), py::arg("ctx_trans"),
+        py::arg("ctx_acc"), py::arg("feat"), py::arg("stream"));
+  m.def("feat_all_host", [](int64_t L, uint64_t text, uint64_t ls, uint64_t ll, py::tuple dfa, uint64_t feat) {
+    const DfaPool D = dfa_from(dfa);
+    py::gil_scoped_release nogil;
+    feat_all_host(L, P<const uint8_t>(text), P<const int64_t>(ls), P<const int32_t>(ll), D, P<uint8_t>(feat)); },
+        py::arg("L"), py::arg("text"), py::arg("ls"), py::arg("ll"), py::arg("dfa"), py::arg("feat"));
+  // sel != 0: sign sel[0, nsel); all: every line; else the uncovered candidates of feat / cov
+  m.def("gap_sig", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t feat, uint64_t cov,
+                      uint64_t sel, int64_t nsel, bool all, uint64_t out_line, uint64_t out_sig, int64_t cap,
+                      uint64_t cnt, uint64_t s, bool dev) {
+    GapSigArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.L = L;
+    A.feat = P<const uint8_t>(feat); A.cov = P<const uint8_t>(cov);
+    A.sel = P<const int32_t>(sel); A.nsel = nsel; A.all = all;
+    A.out_line = P<int32_t>(out_line); A.out_sig = P<int64_t>(out_sig); A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      gap_sig_dev(A, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    gap_sig_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("feat"), py::arg("cov"),
+        py::arg("sel"), py::arg("nsel"), py::arg("all"), py::arg("out_line"), py::arg("out_sig"), py::arg("cap"),
+        py::arg("cnt"), py::arg("stream"), py::arg("dev"));
   m.def("scan_multi", [](uint64_t text, int64_t nbytes, uint64_t ls, uint64_t ll, int64_t nl, py::tuple pass,
                          uint64_t out, int64_t cap, uint64_t cnt, int grid, uint64_t s, bool dev) -> int64_t {
     const ScanPass S = scan_pass_from(pass);

@@ -359,4 +359,34 @@ void blk_index_dev(const int64_t* ls, int64_t L, int64_t nblocks, int32_t* blk, 
 void hits_host(const HitsArgs& A);
 void events_host(const EventsArgs& A);
 void blk_index_host(const int64_t* ls, int64_t L, int64_t nblocks, int32_t* blk);
+// host twin of feat_all_dev: context_feat of every line
+void feat_all_host(int64_t L, const uint8_t* text, const int64_t* ls, const int32_t* ll, const DfaPool& P,
+                   uint8_t* feat);
+}  // namespace lp
+
+// ---- coverage-gap report (gaps.hip): template signatures of the error lines no event explains
+namespace lp {
+struct GapSigArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t L;
+  // self-selecting (sel == null, all == false): line x is signed when gap_candidate(feat[x]) and it
+  // is not covered (cov == null: nothing is covered)
+  const uint8_t* feat = nullptr;   // [L] context features of every line
+  const uint8_t* cov = nullptr;    // [L] or null
+  // listed: sign exactly sel[0, nsel) (out slot i = sel[i]; a line outside [0, L) signs as empty);
+  // all: sign every line (out slot x = line x)
+  const int32_t* sel = nullptr;
+  int64_t nsel = 0;
+  bool all = false;
+  // outputs: (line, signature bit pattern) pairs, the first `cap` of them; cnt[0] += candidates,
+  // cnt[1] += selected lines (all of them: above cap the caller re-runs, as with scan_dev)
+  int32_t* out_line; int64_t* out_sig;
+  int64_t cap;
+  unsigned long long* cnt;   // [2], zeroed by the caller
+};
+void gap_sig_dev(const GapSigArgs& A, uint64_t stream);
+// appends in line order
+void gap_sig_host(const GapSigArgs& A);
 }  // namespace lp

@@ -7,6 +7,9 @@
                                                that is invalid, unsupported on the device path,
                                                or routed to the host fallback (the reference only
                                                finds bad regexes per request, AnalysisService.java:64)
+  gaps      FILE [--patterns DIR] [--device D] [--top N] [--cover events|context]
+                                               the error lines of a log that no pattern of the
+                                               library explains, grouped by line template (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -55,6 +58,17 @@ def cmd_analyze(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_gaps(args, cfg: Config) -> int:
+    from .api import LogParser
+    if args.patterns:
+        cfg = cfg.replace({"pattern.directory": args.patterns})
+    if args.device:
+        cfg = cfg.replace({"engine.device": args.device})
+    lp = LogParser.from_directory(cfg["pattern.directory"], config=cfg)
+    print(json.dumps(lp.gaps_file(args.file, top=args.top, cover=args.cover), ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -77,10 +91,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     v = sub.add_parser("validate", help="compile a pattern library and report problem regexes")
     v.add_argument("directory", nargs="?")
     v.add_argument("--allow", default="nfa", help="comma list of non-DFA kinds not reported (default nfa)")
+    g = sub.add_parser("gaps", help="error lines of a log file that no pattern explains, grouped by template")
+    g.add_argument("file")
+    g.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
+    g.add_argument("--device", help="cuda | cpu | auto")
+    g.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
+    g.add_argument("--cover", choices=("events", "context"), default="context",
+                   help="what an event covers: its own line, or its context window too (default)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
-    return {"analyze": cmd_analyze, "validate": cmd_validate}[args.cmd](args, cfg)
+    return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

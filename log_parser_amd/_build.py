@@ -35,6 +35,7 @@ SOURCES = [
     ("kernels/post_bulk.hip", "hip"),
     ("kernels/request_io.hip", "hip"),
     ("kernels/side_path.hip", "hip"),
+    ("kernels/gaps.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),
     ("io/json_in.cpp", "cpp"),

@@ -15,6 +15,8 @@ to embedders, with what an in-process user needs beyond one call at a time:
   or another parser's library) without crossing PCIe again;
 * ``validate``: the library's compile report (regex kinds, invalid / host-fallback regexes) that
   the reference would only discover as HTTP 500s, request by request (AnalysisService.java:64);
+* ``gaps`` / ``gaps_file``: the error lines of a log that no pattern of the library explains,
+  grouped by line template -- what the library does not cover yet;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -125,6 +127,27 @@ class LogParser:
                                   keep_events=keep_events).run(resident)
 
     # ---- library report -----------------------------------------------------------------------
+    def gaps(self, logs, top: Optional[int] = 20, cover: str = "context") -> dict:
+        """Coverage-gap report of one document (str or bytes): the error lines no pattern explains
+        -- an error keyword or an exception class name, not a stack frame, outside every event
+        (``cover="events"``) or every event's context window (``"context"``) -- grouped by line
+        template, most frequent first (``top=None``: every group). ``Engine.gaps_bytes``; the
+        frequency window is not touched."""
+        if self._batcher is not None:
+            raise RuntimeError("gaps: the batcher owns the engine after submit(); use a parser of its own")
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._lock:
+            if self._batcher is not None:
+                raise RuntimeError("gaps: the batcher owns the engine after submit(); use a parser of its own")
+            return self.engine.gaps_bytes(logs, top=top, cover=cover)
+
+    def gaps_file(self, path: str, top: Optional[int] = 20, cover: str = "context") -> dict:
+        """``gaps`` of a log file, read as ONE document whatever its size (the stream threshold does
+        not apply: the report has one format)."""
+        with open(path, "rb") as f:
+            return self.gaps(f.read(), top=top, cover=cover)
+
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host
         fallback, or of a kind not in ``allow``."""

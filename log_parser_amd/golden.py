@@ -300,3 +300,83 @@ def analyze(logs: str, pattern_sets: List[PatternSet], params: ScoringParams,
     }
     return {"analysisId": str(uuid.uuid4()), "metadata": meta, "events": events,
             "summary": build_summary(events)}
+
+
+# ---------------------------------------------------------------------------------------------
+# Coverage-gap report (an extra: the reference has nothing like it). Which error lines of a log
+# does no pattern explain, grouped by shape? These functions are the specification of
+# ``Engine.gaps_bytes`` and of the template-signature kernel (csrc/kernels/gaps_core.h).
+#
+# Known limits: a hex token without a digit ("deadbeef") is kept as it is, and two different
+# templates may share a 64-bit signature (their lines are then reported as one group).
+
+SIG_MAX_BYTES = 1024
+_FNV_OFFSET = 0xcbf29ce484222325
+_FNV_PRIME = 0x100000001b3
+_TOKEN = re.compile(rb"[0-9A-Za-z]+")
+_DIGIT = re.compile(rb"[0-9]")
+_BLANKS = re.compile(rb"[ \t]+")
+
+
+def line_template(line: bytes) -> bytes:
+    """Shape of a line: of its first ``SIG_MAX_BYTES`` bytes, every maximal ``[0-9A-Za-z]`` run
+    (ASCII) holding a digit becomes ``0``, then every run of space / tab one space; every other
+    byte (bytes >= 0x80 included) is kept."""
+    s = bytes(line[:SIG_MAX_BYTES])
+    s = _TOKEN.sub(lambda m: b"0" if _DIGIT.search(m.group()) else m.group(), s)
+    return _BLANKS.sub(b" ", s)
+
+
+def line_signature(line: bytes) -> int:
+    """FNV-1a-64 of ``line_template(line)``."""
+    h = _FNV_OFFSET
+    for c in line_template(line):
+        h = ((h ^ c) * _FNV_PRIME) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def gap_candidate(line: str) -> bool:
+    """An error keyword or an exception / error class name, and not a stack frame."""
+    return (_find(ERROR_RE, line) or _find(EXC_RE, line)) and not _find(STACK_RE, line)
+
+
+def gaps(logs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optional[int] = 20,
+         cover: str = "context") -> dict:
+    """The gap report from ``analyze``'s events: candidate lines (``gap_candidate``) that no event
+    covers -- ``cover="events"``: the events' own lines; ``"context"``: their context windows too
+    -- grouped by ``line_signature``, most frequent first (ties: first line)."""
+    if cover not in ("events", "context"):
+        raise ValueError("cover must be 'events' or 'context'")
+    if isinstance(logs, (bytes, bytearray, memoryview)):
+        logs = bytes(logs).decode("utf-8", errors="surrogateescape")
+    res = analyze(logs, pattern_sets, params, FrequencyTracker(params))
+    lines = split_lines(logs)
+    covered = [False] * len(lines)
+    for e in res["events"]:
+        x = e["lineNumber"] - 1
+        a, b = x, x + 1
+        if cover == "context":
+            a -= len(e["context"]["linesBefore"] or ())
+            b += len(e["context"]["linesAfter"] or ())
+        for i in range(a, b):
+            covered[i] = True
+    groups: Dict[int, list] = {}
+    n_cand = n_sel = 0
+    for i, line in enumerate(lines):
+        if not gap_candidate(line):
+            continue
+        n_cand += 1
+        if covered[i]:
+            continue
+        n_sel += 1
+        raw = line.encode("utf-8", errors="surrogateescape")
+        g = groups.setdefault(line_signature(raw), [0, i, raw])
+        g[0] += 1
+    order = sorted(groups.items(), key=lambda kv: (-kv[1][0], kv[1][1]))
+    if top is not None:
+        order = order[:max(0, int(top))]
+    return {"totalLines": len(lines), "events": len(res["events"]), "errorLines": n_cand,
+            "uncoveredErrorLines": n_sel, "templates": len(groups),
+            "top": [{"count": c, "firstLine": i + 1, "signature": "%016x" % sig,
+                     "template": line_template(raw).decode("utf-8", errors="replace"),
+                     "example": raw.decode("utf-8", errors="replace")} for sig, (c, i, raw) in order]}

@@ -832,3 +832,69 @@ def score_fused(ev_line, ev_pat, ev_seg, ev_rank, ev_fkey, freq_carry, st_tuple,
     else:
         N.score_host(*args)
     return out, fac
+
+
+# ---------------------------------------------------------------------------------------------
+# coverage-gap report (csrc/kernels/gaps.hip): features of every line, template signatures
+
+SIG_MAX_BYTES = 1024    # a line's template covers its first KiB (csrc/kernels/gaps_core.h)
+
+
+def context_features_all(text, line_start, line_len, dfa_tuple,
+                         ctx_ext: Tuple[int, int] = (1 << 30, 1 << 30)) -> torch.Tensor:
+    """Context features of EVERY line (uint8[L]; bit0 ERROR, bit1 WARN when not ERROR, bit2 stack
+    frame, bit3 exception / error class name): k_feat_cov without a coverage filter."""
+    L = line_start.numel()
+    feat = torch.empty(L, dtype=torch.uint8, device=text.device)
+    if L == 0:
+        return feat
+    if text.is_cuda:
+        N.feat_all_dev(L, text.data_ptr(), line_start.data_ptr(), line_len.data_ptr(), dfa_tuple, ctx_ext[0],
+                       ctx_ext[1], feat.data_ptr(), _s(text))
+    else:
+        N.feat_all_host(L, text.data_ptr(), line_start.data_ptr(), line_len.data_ptr(), dfa_tuple, feat.data_ptr())
+    return feat
+
+
+def _gap_sig(text, line_start, line_len, feat, cov, sel, every: bool, cap: int):
+    """k_gap_sig / its host twin with the capacity protocol of ``scan``: (line, sig, candidates,
+    selected), one read of the two counters per run."""
+    dev = text.device
+    L = line_start.numel()
+    if sel is not None:
+        sel = sel.to(device=dev, dtype=torch.int32).contiguous()
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_sig = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        N.gap_sig(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, _p(feat), _p(cov),
+                  _p(sel), 0 if sel is None else sel.numel(), every, out_line.data_ptr(), out_sig.data_ptr(), cap,
+                  cnt.data_ptr(), _s(text), text.is_cuda)
+        n_cand, n = cnt.tolist()
+        if n <= cap:
+            return out_line[:n], out_sig[:n], n_cand
+        cap = n
+
+
+def line_signatures(text, line_start, line_len, sel: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Template signatures (int64 bit patterns of FNV-1a-64, ``golden.line_signature``) of the
+    lines ``sel`` (int32, any order, repeats allowed), or of every line."""
+    n = line_start.numel() if sel is None else sel.numel()
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=text.device)
+    return _gap_sig(text, line_start, line_len, None, None, sel, sel is None, n)[1]
+
+
+def gap_lines(text, line_start, line_len, feat: torch.Tensor, cov: Optional[torch.Tensor],
+              cap: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """The candidate lines of ``feat`` (uint8[L], every line's context features) that ``cov``
+    (uint8[L], or None: nothing covered) does not cover: (line int32[n], signature int64[n],
+    number of candidates). GPU: the pairs come in no particular order; CPU: in line order."""
+    if line_start.numel() == 0:
+        return (torch.empty(0, dtype=torch.int32, device=text.device),
+                torch.empty(0, dtype=torch.int64, device=text.device), 0)
+    if feat.dtype != torch.uint8 or feat.numel() < line_start.numel() or not feat.is_contiguous():
+        raise ValueError("gap_lines: feat must be contiguous uint8[L]")
+    if cov is not None and (cov.dtype != torch.uint8 or cov.numel() < line_start.numel() or not cov.is_contiguous()):
+        raise ValueError("gap_lines: cov must be contiguous uint8[L]")
+    return _gap_sig(text, line_start, line_len, feat, cov, None, False, cap)
