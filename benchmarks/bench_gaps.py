@@ -5,7 +5,13 @@ Needs a GPU: the times are device-event times, there is no CPU fallback. Prints 
 the median over ``--steps`` runs (after ``--warmup``) of ``Engine.gaps_document`` (everything of
 ``gaps_bytes`` after the text is staged) and of ``run_document``, and their ratio.
 
-Kernel times (k_gap_sig, k_feat_cov) come from a separate traced run, e.g.
+``--stream CHUNK_BYTES`` measures the chunked report instead (``GapAccumulator.add_stream`` +
+``report``, what ``LogParser.gaps_stream`` runs) against ``gaps_document`` on the same data in the
+same run. The stream starts from the host bytes, so its time includes staging and the H2D copies
+that ``gaps_document`` (text already on the device) does not pay.
+
+Kernel times (k_gap_sig, k_feat_cov; with ``--stream`` also k_gap_fold, k_gap_winners) come from a
+separate traced run, e.g.
 ``rocprofv3 --kernel-trace --stats -d OUT -- python benchmarks/bench_gaps.py --gaps-only --steps 3 --warmup 1``.
 """
 from __future__ import annotations
@@ -48,6 +54,8 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cover", choices=("events", "context"), default="context")
     ap.add_argument("--gaps-only", action="store_true", help="skip run_document (for a kernel trace of the report)")
+    ap.add_argument("--stream", type=int, default=0, metavar="CHUNK_BYTES",
+                    help="measure the chunked report (gaps_stream) against gaps_document")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("bench_gaps: needs a GPU", file=sys.stderr)
@@ -65,6 +73,23 @@ def main() -> int:
     def document():
         return eng.run_document(text, n)
 
+    if args.stream:
+        from log_parser_amd.gapreport import GapAccumulator
+        srep = {}
+
+        def stream():
+            acc = GapAccumulator(eng, cover=args.cover)
+            acc.add_stream(data, chunk_bytes=args.stream)
+            srep.clear()
+            srep.update(acc.report(top=20))
+
+        s = _median_ms(stream, args.warmup, args.steps, dev)
+        g = float("nan") if args.gaps_only else _median_ms(gaps, args.warmup, args.steps, dev)
+        print(json.dumps({"config": f"gaps-stream-{args.lines}-lines-256-patterns", "bytes": n, "steps": args.steps,
+                          "chunk_bytes": args.stream, "gaps_stream_ms": round(s, 3), "gaps_document_ms": round(g, 3),
+                          "ratio": round(s / g, 3), "same_report": None if args.gaps_only else srep == rep,
+                          "report": {k: v for k, v in srep.items() if k != "top"}}))
+        return 0
     g = _median_ms(gaps, args.warmup, args.steps, dev)
     # (a kernel trace of the report alone: run_document's own k_feat_cov launches would mix in)
     d = _median_ms(document, args.warmup, args.steps, dev) if not args.gaps_only else float("nan")

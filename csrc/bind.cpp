@@ -72,6 +72,30 @@ static DfaPool dfa_from(const py::tuple& t) {
   return D;
 }
 
+// (key, count, first, docs, last_doc, used, cap) of a signature group table (gap_table.h)
+static GapTab gt_from(const py::tuple& t) {
+  GapTab T;
+  T.key = P<int64_t>(t[0].cast<uint64_t>());
+  T.count = P<unsigned long long>(t[1].cast<uint64_t>());
+  T.first = P<long long>(t[2].cast<uint64_t>());
+  T.docs = P<int32_t>(t[3].cast<uint64_t>());
+  T.last_doc = P<int32_t>(t[4].cast<uint64_t>());
+  T.used = P<unsigned long long>(t[5].cast<uint64_t>());
+  T.cap = t[6].cast<int64_t>();
+  return T;
+}
+
+// (sig, count, first, docs, last_doc) row columns
+static GapRows gr_from(const py::tuple& t) {
+  GapRows R;
+  R.sig = P<int64_t>(t[0].cast<uint64_t>());
+  R.count = P<int64_t>(t[1].cast<uint64_t>());
+  R.first = P<int64_t>(t[2].cast<uint64_t>());
+  R.docs = P<int32_t>(t[3].cast<uint64_t>());
+  R.last_doc = P<int32_t>(t[4].cast<uint64_t>());
+  return R;
+}
+
 static ScoreTables st_from(const py::tuple& t) {
   ScoreTables T;
   int i = 0;
@@ -1090,6 +1114,48 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("feat"), py::arg("cov"),
         py::arg("sel"), py::arg("nsel"), py::arg("all"), py::arg("out_line"), py::arg("out_sig"), py::arg("cap"),
         py::arg("cnt"), py::arg("stream"), py::arg("dev"));
+  // ---- signature group table (gap_table.hip): the report's grouping across chunks and documents
+  m.def("gap_fold", [](py::tuple tab, uint64_t sig, uint64_t ord, int64_t n, int doc, uint64_t s, bool dev, int tile) {
+    const GapTab T = gt_from(tab);
+    if (dev) {
+      gap_fold_dev(T, P<const int64_t>(sig), P<const int64_t>(ord), n, doc, s, tile);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    gap_fold_host(T, P<const int64_t>(sig), P<const int64_t>(ord), n, doc); },
+        py::arg("tab"), py::arg("sig"), py::arg("ord"), py::arg("n"), py::arg("doc"), py::arg("stream"), py::arg("dev"),
+        py::arg("tile") = 0);
+  m.def("gap_winners", [](py::tuple tab, uint64_t sig, uint64_t ord, int64_t n, uint64_t out, uint64_t cnt, uint64_t s,
+                          bool dev) {
+    const GapTab T = gt_from(tab);
+    if (dev) {
+      gap_winners_dev(T, P<const int64_t>(sig), P<const int64_t>(ord), n, P<int64_t>(out), P<unsigned long long>(cnt), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    gap_winners_host(T, P<const int64_t>(sig), P<const int64_t>(ord), n, P<int64_t>(out), P<unsigned long long>(cnt)); },
+        py::arg("tab"), py::arg("sig"), py::arg("ord"), py::arg("n"), py::arg("out"), py::arg("cnt"), py::arg("stream"),
+        py::arg("dev"));
+  m.def("gap_rows", [](py::tuple tab, py::tuple rows, int64_t out_cap, uint64_t cnt, uint64_t s, bool dev) {
+    const GapTab T = gt_from(tab);
+    const GapRows R = gr_from(rows);
+    if (dev) {
+      gap_rows_dev(T, R, out_cap, P<unsigned long long>(cnt), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    gap_rows_host(T, R, out_cap, P<unsigned long long>(cnt)); },
+        py::arg("tab"), py::arg("rows"), py::arg("out_cap"), py::arg("cnt"), py::arg("stream"), py::arg("dev"));
+  m.def("gap_reinsert", [](py::tuple tab, py::tuple rows, int64_t n, uint64_t s, bool dev) {
+    const GapTab T = gt_from(tab);
+    const GapRows R = gr_from(rows);
+    if (dev) {
+      gap_reinsert_dev(T, R, n, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    gap_reinsert_host(T, R, n); },
+        py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
   m.def("scan_multi", [](uint64_t text, int64_t nbytes, uint64_t ls, uint64_t ll, int64_t nl, py::tuple pass,
                          uint64_t out, int64_t cap, uint64_t cnt, int grid, uint64_t s, bool dev) -> int64_t {
     const ScanPass S = scan_pass_from(pass);

@@ -390,3 +390,31 @@ void gap_sig_dev(const GapSigArgs& A, uint64_t stream);
 // appends in line order
 void gap_sig_host(const GapSigArgs& A);
 }  // namespace lp
+
+// ---- signature group table (gap_table.hip): the grouping of the report across chunks and documents
+#include "gap_table.h"
+namespace lp {
+struct GapRows {             // rows of a table, or the rows to put into one
+  int64_t* sig; int64_t* count; int64_t* first;
+  int32_t* docs; int32_t* last_doc;
+};
+// n pairs (sig[i], ord[i]) of document `doc` into the table; the caller keeps 2 * (used + n) <= cap,
+// launches one document at a time and never a smaller document number than before. tile: pairs per
+// block (256..2048, a multiple of 256), 0: chosen from n
+void gap_fold_dev(const GapTab& T, const int64_t* sig, const int64_t* ord, int64_t n, int doc, uint64_t stream,
+                  int tile = 0);
+// after the fold of the same pairs: out[*cnt ...] = i for every pair whose ordinal is its group's
+// smallest (out holds n entries; *cnt grows by the number appended)
+void gap_winners_dev(const GapTab& T, const int64_t* sig, const int64_t* ord, int64_t n, int64_t* out,
+                     unsigned long long* cnt, uint64_t stream);
+// the occupied slots as rows, in no particular order: the first out_cap of them; *cnt += all of them
+void gap_rows_dev(const GapTab& T, const GapRows& R, int64_t out_cap, unsigned long long* cnt, uint64_t stream);
+// n rows of distinct signatures into a table that holds none of them (growth); used[0] is left to
+// the caller, who knows it is n
+void gap_reinsert_dev(const GapTab& T, const GapRows& R, int64_t n, uint64_t stream);
+void gap_fold_host(const GapTab& T, const int64_t* sig, const int64_t* ord, int64_t n, int doc);
+void gap_winners_host(const GapTab& T, const int64_t* sig, const int64_t* ord, int64_t n, int64_t* out,
+                      unsigned long long* cnt);
+void gap_rows_host(const GapTab& T, const GapRows& R, int64_t out_cap, unsigned long long* cnt);
+void gap_reinsert_host(const GapTab& T, const GapRows& R, int64_t n);
+}  // namespace lp

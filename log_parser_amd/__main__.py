@@ -7,9 +7,11 @@
                                                that is invalid, unsupported on the device path,
                                                or routed to the host fallback (the reference only
                                                finds bad regexes per request, AnalysisService.java:64)
-  gaps      FILE [--patterns DIR] [--device D] [--top N] [--cover events|context]
+  gaps      FILE [FILE ...] [--patterns DIR] [--device D] [--top N] [--cover events|context] [--stream]
                                                the error lines of a log that no pattern of the
-                                               library explains, grouped by line template (JSON)
+                                               library explains, grouped by line template (JSON);
+                                               several files: the corpus report, in argument order;
+                                               --stream: one file in chunks (any size)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -65,7 +67,21 @@ def cmd_gaps(args, cfg: Config) -> int:
     if args.device:
         cfg = cfg.replace({"engine.device": args.device})
     lp = LogParser.from_directory(cfg["pattern.directory"], config=cfg)
-    print(json.dumps(lp.gaps_file(args.file, top=args.top, cover=args.cover), ensure_ascii=False))
+    if len(args.file) > 1:
+        if args.stream:
+            print("gaps: --stream takes one file", file=sys.stderr)
+            return 2
+
+        def docs():
+            for path in args.file:
+                with open(path, "rb") as f:
+                    yield f.read()
+        rep = lp.gaps_corpus(docs(), top=args.top, cover=args.cover)
+    elif args.stream:
+        rep = lp.gaps_stream(args.file[0], top=args.top, cover=args.cover)
+    else:
+        rep = lp.gaps_file(args.file[0], top=args.top, cover=args.cover)
+    print(json.dumps(rep, ensure_ascii=False))
     return 0
 
 
@@ -92,9 +108,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     v.add_argument("directory", nargs="?")
     v.add_argument("--allow", default="nfa", help="comma list of non-DFA kinds not reported (default nfa)")
     g = sub.add_parser("gaps", help="error lines of a log file that no pattern explains, grouped by template")
-    g.add_argument("file")
+    g.add_argument("file", nargs="+", help="one log file, or several: the corpus report in argument order")
     g.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
     g.add_argument("--device", help="cuda | cpu | auto")
+    g.add_argument("--stream", action="store_true", help="one file processed in chunks (same report)")
     g.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
     g.add_argument("--cover", choices=("events", "context"), default="context",
                    help="what an event covers: its own line, or its context window too (default)")

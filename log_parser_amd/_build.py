@@ -36,6 +36,7 @@ SOURCES = [
     ("kernels/request_io.hip", "hip"),
     ("kernels/side_path.hip", "hip"),
     ("kernels/gaps.hip", "hip"),
+    ("kernels/gap_table.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),
     ("io/json_in.cpp", "cpp"),

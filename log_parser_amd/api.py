@@ -16,12 +16,15 @@ to embedders, with what an in-process user needs beyond one call at a time:
 * ``validate``: the library's compile report (regex kinds, invalid / host-fallback regexes) that
   the reference would only discover as HTTP 500s, request by request (AnalysisService.java:64);
 * ``gaps`` / ``gaps_file``: the error lines of a log that no pattern of the library explains,
-  grouped by line template -- what the library does not cover yet;
+  grouped by line template -- what the library does not cover yet; ``gaps_stream`` /
+  ``gaps_resident`` for one log too large for one piece, ``gaps_corpus`` / ``gap_accumulator``
+  for many documents (which templates are most common across them, and in how many);
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import mmap
 import os
@@ -147,6 +150,59 @@ class LogParser:
         not apply: the report has one format)."""
         with open(path, "rb") as f:
             return self.gaps(f.read(), top=top, cover=cover)
+
+    @contextlib.contextmanager
+    def _engine_guard(self, who: str = "gaps"):
+        """The batcher guard and the lock of ``gaps``, around one use of the engine."""
+        msg = who + ": the batcher owns the engine after submit(); use a parser of its own"
+        if self._batcher is not None:
+            raise RuntimeError(msg)
+        with self._lock:
+            if self._batcher is not None:
+                raise RuntimeError(msg)
+            yield
+
+    def gap_accumulator(self, cover: str = "context"):
+        """A ``gapreport.GapAccumulator`` on this parser's engine for callers that feed documents
+        over time (``add_document`` / ``add_stream`` / ``add_resident``, then ``report``); each of
+        its calls runs under the batcher guard and the lock of ``gaps``."""
+        from .gapreport import GapAccumulator
+        with self._engine_guard("gap_accumulator"):
+            return GapAccumulator(self.engine, cover=cover, guard=self._engine_guard)
+
+    def gaps_stream(self, src_or_path, chunk_bytes: Optional[int] = None, top: Optional[int] = 20,
+                    cover: str = "context") -> dict:
+        """``gaps`` of ONE large log processed in line-aligned chunks with halos (the chunks of
+        ``parse_stream``): a bytes-like source, or the path of a file (mmap'd as ``parse_file``
+        does). The report is exactly the one-document report, whatever the chunk size."""
+        if isinstance(src_or_path, (str, os.PathLike)):
+            size = os.path.getsize(src_or_path)
+            with open(src_or_path, "rb") as f:
+                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
+                try:
+                    return self.gaps_stream(mm, chunk_bytes=chunk_bytes, top=top, cover=cover)
+                finally:
+                    if size:
+                        mm.close()
+        acc = self.gap_accumulator(cover)
+        acc.add_stream(src_or_path, chunk_bytes)
+        return acc.report(top)
+
+    def gaps_resident(self, resident, top: Optional[int] = 20, cover: str = "context") -> dict:
+        """``gaps`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        acc = self.gap_accumulator(cover)
+        acc.add_resident(resident)
+        return acc.report(top)
+
+    def gaps_corpus(self, docs, top: Optional[int] = 20, cover: str = "context") -> dict:
+        """Coverage-gap report of many documents (an iterable of str or bytes), each analysed on
+        its own: the totals summed, ``documents``, and per group also ``documents`` (how many
+        documents it occurs in) and ``firstDocument`` (0-based; ``firstLine`` counts within it).
+        Exactly one document gives ``gaps`` of it. ``golden.gaps_corpus`` is the specification."""
+        acc = self.gap_accumulator(cover)
+        for d in docs:
+            acc.add_document(d)
+        return acc.report(top)
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

@@ -340,11 +340,9 @@ def gap_candidate(line: str) -> bool:
     return (_find(ERROR_RE, line) or _find(EXC_RE, line)) and not _find(STACK_RE, line)
 
 
-def gaps(logs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optional[int] = 20,
-         cover: str = "context") -> dict:
-    """The gap report from ``analyze``'s events: candidate lines (``gap_candidate``) that no event
-    covers -- ``cover="events"``: the events' own lines; ``"context"``: their context windows too
-    -- grouped by ``line_signature``, most frequent first (ties: first line)."""
+def _gap_groups(logs, pattern_sets: List[PatternSet], params: ScoringParams, cover: str):
+    """One document's part of the report: (lines, events, candidates, uncovered candidates,
+    {signature: [count, first line (0-based), raw first line]})."""
     if cover not in ("events", "context"):
         raise ValueError("cover must be 'events' or 'context'")
     if isinstance(logs, (bytes, bytearray, memoryview)):
@@ -372,11 +370,53 @@ def gaps(logs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optio
         raw = line.encode("utf-8", errors="surrogateescape")
         g = groups.setdefault(line_signature(raw), [0, i, raw])
         g[0] += 1
+    return len(lines), len(res["events"]), n_cand, n_sel, groups
+
+
+def _gap_group_fields(sig: int, count: int, line: int, raw: bytes) -> dict:
+    return {"count": count, "firstLine": line + 1, "signature": "%016x" % sig,
+            "template": line_template(raw).decode("utf-8", errors="replace"),
+            "example": raw.decode("utf-8", errors="replace")}
+
+
+def gaps(logs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optional[int] = 20,
+         cover: str = "context") -> dict:
+    """The gap report from ``analyze``'s events: candidate lines (``gap_candidate``) that no event
+    covers -- ``cover="events"``: the events' own lines; ``"context"``: their context windows too
+    -- grouped by ``line_signature``, most frequent first (ties: first line)."""
+    n_lines, n_events, n_cand, n_sel, groups = _gap_groups(logs, pattern_sets, params, cover)
     order = sorted(groups.items(), key=lambda kv: (-kv[1][0], kv[1][1]))
     if top is not None:
         order = order[:max(0, int(top))]
-    return {"totalLines": len(lines), "events": len(res["events"]), "errorLines": n_cand,
+    return {"totalLines": n_lines, "events": n_events, "errorLines": n_cand,
             "uncoveredErrorLines": n_sel, "templates": len(groups),
-            "top": [{"count": c, "firstLine": i + 1, "signature": "%016x" % sig,
-                     "template": line_template(raw).decode("utf-8", errors="replace"),
-                     "example": raw.decode("utf-8", errors="replace")} for sig, (c, i, raw) in order]}
+            "top": [_gap_group_fields(sig, c, i, raw) for sig, (c, i, raw) in order]}
+
+
+def gaps_corpus(docs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optional[int] = 20,
+                cover: str = "context") -> dict:
+    """The gap report of a corpus: every document (str or bytes) is analysed on its own -- no
+    context window and no template crosses a document border -- and the groups are merged by
+    signature. Exactly one document: ``gaps`` of it. Otherwise the totals are summed, and
+    ``documents`` counts the documents; every group also carries ``documents`` (how many
+    documents it occurs in) and ``firstDocument`` (0-based; ``firstLine`` is 1-based within it).
+    Most frequent first, ties by (first document, first line)."""
+    docs = list(docs)
+    if len(docs) == 1:
+        return gaps(docs[0], pattern_sets, params, top, cover)
+    tot = [0, 0, 0, 0]
+    merged: Dict[int, list] = {}                # signature -> [count, first document, first line, raw, documents]
+    for d, logs in enumerate(docs):
+        *nums, groups = _gap_groups(logs, pattern_sets, params, cover)
+        tot = [a + b for a, b in zip(tot, nums)]
+        for sig, (c, i, raw) in groups.items():
+            g = merged.setdefault(sig, [0, d, i, raw, 0])
+            g[0] += c
+            g[4] += 1
+    order = sorted(merged.items(), key=lambda kv: (-kv[1][0], kv[1][1], kv[1][2]))
+    if top is not None:
+        order = order[:max(0, int(top))]
+    return {"totalLines": tot[0], "events": tot[1], "errorLines": tot[2], "uncoveredErrorLines": tot[3],
+            "templates": len(merged), "top": [
+                {**_gap_group_fields(sig, c, i, raw), "documents": nd, "firstDocument": d}
+                for sig, (c, d, i, raw, nd) in order], "documents": len(docs)}

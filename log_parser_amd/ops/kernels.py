@@ -898,3 +898,120 @@ def gap_lines(text, line_start, line_len, feat: torch.Tensor, cov: Optional[torc
     if cov is not None and (cov.dtype != torch.uint8 or cov.numel() < line_start.numel() or not cov.is_contiguous()):
         raise ValueError("gap_lines: cov must be contiguous uint8[L]")
     return _gap_sig(text, line_start, line_len, feat, cov, None, False, cap)
+
+
+# ---------------------------------------------------------------------------------------------
+# signature group table (csrc/kernels/gap_table.hip): the report's grouping across launches
+
+GT_EMPTY = -(1 << 63)       # empty marker of the key column (csrc/kernels/gap_table.h)
+GT_TILE = 2048              # pairs per block of k_gap_fold at most (small launches get smaller tiles)
+GT_LDS_SLOTS = 1024         # slots of its LDS table: more distinct signatures in a tile go to HBM directly
+_I64_MAX = (1 << 63) - 1
+
+
+class GapTable:
+    """Device-resident groups of (signature, ordinal) pairs: per signature its count, its smallest
+    ordinal and the number of documents it occurs in, kept across ``fold`` calls (the chunks of a
+    stream, the documents of a corpus). GPU: k_gap_fold / k_gap_winners / k_gap_rows; CPU: their
+    host twins on the same layout.
+
+    Capacity: before ``n`` pairs are folded, ``2 * (used + n) <= cap`` holds -- the table grows
+    (rows of the old one re-inserted into one at least twice as large) when it does not. ``used``
+    is bounded on the host by the number of pairs folded so far; the device counter is read only
+    when that bound crosses the limit, so steady folding reads nothing but the winners' count."""
+
+    def __init__(self, device, cap: int = 1 << 12, tile: int = 0):
+        """``tile``: pairs per block of k_gap_fold (256..GT_TILE, a multiple of 256) instead of the
+        size the launch picks from its number of pairs (tests: the paths of a full-size tile
+        without millions of pairs)."""
+        cap = max(2, int(cap))
+        self.tile = int(tile)
+        if self.tile and (self.tile < 256 or self.tile > GT_TILE or self.tile % 256):
+            raise ValueError("GapTable: tile must be 256..%d, a multiple of 256" % GT_TILE)
+        if cap & (cap - 1):
+            raise ValueError("GapTable: cap must be a power of two")
+        self.device = torch.device(device)
+        self._bound = 0             # host upper bound of the occupied slots
+        self._last_doc = -1
+        self._alloc(cap)
+
+    def _alloc(self, cap: int) -> None:
+        dev = self.device
+        self.cap = cap
+        self._key = torch.full((cap + 1,), GT_EMPTY, dtype=torch.int64, device=dev)
+        self._key[cap] = 0          # the side slot of the signature that equals the marker: unclaimed
+        self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._first = torch.full((cap + 1,), _I64_MAX, dtype=torch.int64, device=dev)
+        self._docs = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
+        self._last = torch.full((cap + 1,), -1, dtype=torch.int32, device=dev)
+        self._used = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def _tab(self):
+        return (self._key.data_ptr(), self._count.data_ptr(), self._first.data_ptr(), self._docs.data_ptr(),
+                self._last.data_ptr(), self._used.data_ptr(), self.cap)
+
+    @property
+    def _cuda(self) -> bool:
+        return self.device.type == "cuda"
+
+    @property
+    def used(self) -> int:
+        """Occupied slots (a read of the device counter)."""
+        used, lost = self._used.tolist()
+        if lost:
+            raise RuntimeError("GapTable: %d pairs found no slot (capacity rule broken)" % lost)
+        self._bound = used
+        return used
+
+    def _rows(self, n: int):
+        dev = self.device
+        cols = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+                torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                torch.empty(n, dtype=torch.int32, device=dev))
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        N.gap_rows(self._tab(), tuple(c.data_ptr() for c in cols), n, cnt.data_ptr(), _s(self._key), self._cuda)
+        if int(cnt.item()) != n:
+            raise RuntimeError("GapTable: %d occupied slots, the counter says %d" % (int(cnt.item()), n))
+        return cols
+
+    def rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(signature int64, count int64, smallest ordinal int64, documents int32) of every group,
+        in no particular order."""
+        return self._rows(self.used)[:4]
+
+    def _grow(self, used: int, cap: int) -> None:
+        rows = self._rows(used)
+        self._alloc(cap)
+        if used:
+            N.gap_reinsert(self._tab(), tuple(c.data_ptr() for c in rows), used, _s(self._key), self._cuda)
+            self._used[0] = used
+
+    def fold(self, sig: torch.Tensor, ord: torch.Tensor, doc: int = 0) -> torch.Tensor:
+        """Fold the pairs (sig[i], ord[i]) of document ``doc`` (one document per call, numbers never
+        decreasing) into the table. Returns the indices (int64, no particular order) of the pairs
+        that hold their group's smallest ordinal after this call."""
+        n = sig.numel()
+        if ord.numel() != n:
+            raise ValueError("GapTable.fold: sig and ord differ in length")
+        doc = int(doc)
+        if doc < self._last_doc or not 0 <= doc < (1 << 31):
+            raise ValueError("GapTable.fold: document numbers must not decrease")
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64, device=self.device)
+        sig = sig.to(device=self.device, dtype=torch.int64).contiguous()
+        ord = ord.to(device=self.device, dtype=torch.int64).contiguous()
+        if 2 * (self._bound + n) > self.cap:
+            used = self.used                                    # the bound crossed the limit: the real count
+            if 2 * (used + n) > self.cap:
+                cap = self.cap
+                while 2 * (used + n) > cap:
+                    cap *= 2
+                self._grow(used, cap)
+        self._bound += n
+        self._last_doc = doc
+        tab, st = self._tab(), _s(self._key)
+        N.gap_fold(tab, sig.data_ptr(), ord.data_ptr(), n, doc, st, self._cuda, self.tile)
+        out = torch.empty(n, dtype=torch.int64, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        N.gap_winners(tab, sig.data_ptr(), ord.data_ptr(), n, out.data_ptr(), cnt.data_ptr(), st, self._cuda)
+        return out[:int(cnt.item())]
