@@ -1156,6 +1156,46 @@ PYBIND11_MODULE(_lpnative, m) {
     py::gil_scoped_release nogil;
     gap_reinsert_host(T, R, n); },
         py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
+  // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
+  m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
+                       bool dev) {
+    if (dev) {
+      ts_parse_dev(P<const uint8_t>(text), tbytes, P<const int64_t>(ls), P<const int32_t>(ll), L, P<int64_t>(out), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    ts_parse_host(P<const uint8_t>(text), tbytes, P<const int64_t>(ls), P<const int32_t>(ll), L, P<int64_t>(out)); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("out"),
+        py::arg("stream"), py::arg("dev"));
+  m.def("tl_fill_tmp_words", &tl_fill_tmp_words, py::arg("L"));
+  m.def("tl_fill", [](uint64_t ts, int64_t L, int64_t carry_last, int64_t carry_top, uint64_t eff, uint64_t ooo,
+                      uint64_t tmp, uint64_t s, bool dev) {
+    if (dev) {
+      tl_fill_dev(P<const int64_t>(ts), L, carry_last, carry_top, P<int64_t>(eff), P<unsigned long long>(ooo),
+                  P<int64_t>(tmp), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    tl_fill_host(P<const int64_t>(ts), L, carry_last, carry_top, P<int64_t>(eff), P<unsigned long long>(ooo)); },
+        py::arg("ts"), py::arg("L"), py::arg("carry_last"), py::arg("carry_top"), py::arg("eff"), py::arg("ooo"),
+        py::arg("tmp"), py::arg("stream"), py::arg("dev"));
+  m.def("tl_hist", [](uint64_t eff, uint64_t feat, int64_t L, uint64_t ev_line, uint64_t ev_pat, int64_t E,
+                      uint64_t sev_index, int64_t npat, int S, int64_t t0, int64_t W, int64_t nb, uint64_t hist,
+                      uint64_t s, bool dev) {
+    TlHistArgs A;
+    A.eff = P<const int64_t>(eff); A.feat = P<const uint8_t>(feat); A.L = L;
+    A.ev_line = P<const int32_t>(ev_line); A.ev_pat = P<const int32_t>(ev_pat); A.E = E;
+    A.sev_index = P<const int32_t>(sev_index); A.P = npat; A.S = S;
+    A.t0 = t0; A.W = W; A.nb = nb; A.hist = P<int64_t>(hist);
+    if (dev) {
+      tl_hist_dev(A, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    tl_hist_host(A); },
+        py::arg("eff"), py::arg("feat"), py::arg("L"), py::arg("ev_line"), py::arg("ev_pat"), py::arg("E"),
+        py::arg("sev_index"), py::arg("npat"), py::arg("S"), py::arg("t0"), py::arg("W"), py::arg("nb"),
+        py::arg("hist"), py::arg("stream"), py::arg("dev"));
   m.def("scan_multi", [](uint64_t text, int64_t nbytes, uint64_t ls, uint64_t ll, int64_t nl, py::tuple pass,
                          uint64_t out, int64_t cap, uint64_t cnt, int grid, uint64_t s, bool dev) -> int64_t {
     const ScanPass S = scan_pass_from(pass);

@@ -418,3 +418,36 @@ void gap_winners_host(const GapTab& T, const int64_t* sig, const int64_t* ord, i
 void gap_rows_host(const GapTab& T, const GapRows& R, int64_t out_cap, unsigned long long* cnt);
 void gap_reinsert_host(const GapTab& T, const GapRows& R, int64_t n);
 }  // namespace lp
+
+// ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
+namespace lp {
+// out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN
+// (ts_core.h line_ts_at); text: 16-byte aligned on the device, tbytes: bytes of it that may be read
+void ts_parse_dev(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, int64_t* out,
+                  uint64_t stream);
+void ts_parse_host(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, int64_t* out);
+// forward fill and out-of-order count over the stamps ts[0, L) in line order: eff[i] = the stamp
+// of the nearest stamped line at or before i, else carry_last (the same of the earlier chunks, or
+// TS_NONE); *ooo += the stamped lines whose stamp is below the largest stamp before them
+// (carry_top: the largest of the earlier chunks, or TS_NONE). tmp: tl_fill_tmp_words(L) words.
+void tl_fill_dev(const int64_t* ts, int64_t L, int64_t carry_last, int64_t carry_top, int64_t* eff,
+                 unsigned long long* ooo, int64_t* tmp, uint64_t stream);
+int64_t tl_fill_tmp_words(int64_t L);
+void tl_fill_host(const int64_t* ts, int64_t L, int64_t carry_last, int64_t carry_top, int64_t* eff,
+                  unsigned long long* ooo);
+struct TlHistArgs {
+  const int64_t* eff;        // [L] effective time of every line, TS_NONE: undated
+  const uint8_t* feat;       // [L] context features of every line
+  int64_t L;
+  const int32_t* ev_line;    // [E] the events' lines (an event outside [0, L) is not counted)
+  const int32_t* ev_pat;     // [E] their patterns
+  int64_t E;
+  const int32_t* sev_index;  // [P] severity number of every pattern
+  int64_t P;
+  int S;                     // distinct severities
+  int64_t t0, W, nb;         // bucket b covers [t0 + b * W, t0 + (b + 1) * W) milliseconds
+  int64_t* hist;             // [nb][3 + S], added to: lines, error lines, events, one column per severity
+};
+void tl_hist_dev(const TlHistArgs& A, uint64_t stream);
+void tl_hist_host(const TlHistArgs& A);
+}  // namespace lp

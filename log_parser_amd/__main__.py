@@ -12,6 +12,10 @@
                                                library explains, grouped by line template (JSON);
                                                several files: the corpus report, in argument order;
                                                --stream: one file in chunks (any size)
+  timeline  FILE [--patterns DIR] [--device D] [--bucket SECONDS] [--stream]
+                                               when the lines, error lines and events of a log
+                                               happened: the stamps at the head of its lines, counts
+                                               per time bucket (JSON); --stream: in chunks (any size)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -85,6 +89,23 @@ def cmd_gaps(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_timeline(args, cfg: Config) -> int:
+    from .api import LogParser
+    if args.patterns:
+        cfg = cfg.replace({"pattern.directory": args.patterns})
+    if args.device:
+        cfg = cfg.replace({"engine.device": args.device})
+    lp = LogParser.from_directory(cfg["pattern.directory"], config=cfg)
+    call = lp.timeline_stream if args.stream else lp.timeline_file
+    try:
+        rep = call(args.file, bucket_seconds=args.bucket)
+    except ValueError as e:                 # the span of the log against max_buckets
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -115,10 +136,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     g.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
     g.add_argument("--cover", choices=("events", "context"), default="context",
                    help="what an event covers: its own line, or its context window too (default)")
+    t = sub.add_parser("timeline", help="lines, error lines and events of a log file per time bucket")
+    t.add_argument("file")
+    t.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
+    t.add_argument("--device", help="cuda | cpu | auto")
+    t.add_argument("--bucket", type=int, default=60, metavar="SECONDS", help="bucket width (default 60)")
+    t.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
-    return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps}[args.cmd](args, cfg)
+    return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
+            "timeline": cmd_timeline}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

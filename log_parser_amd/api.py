@@ -19,6 +19,9 @@ to embedders, with what an in-process user needs beyond one call at a time:
   grouped by line template -- what the library does not cover yet; ``gaps_stream`` /
   ``gaps_resident`` for one log too large for one piece, ``gaps_corpus`` / ``gap_accumulator``
   for many documents (which templates are most common across them, and in how many);
+* ``timeline`` / ``timeline_file``: when the lines, error lines and events of a log happened --
+  the stamps of the lines read on the device, counts per time bucket; ``timeline_stream`` /
+  ``timeline_resident`` for one log too large for one piece;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -203,6 +206,56 @@ class LogParser:
         for d in docs:
             acc.add_document(d)
         return acc.report(top)
+
+    # ---- log timeline -------------------------------------------------------------------------
+    def timeline(self, logs, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
+        """When did what happen in one document (str or bytes)? The stamp at the head of every line
+        (ISO-8601 / RFC 3339 shapes, UTC unless a zone follows) dates the line; a line without one
+        takes the time of the nearest earlier stamped line. The report counts lines, error lines,
+        events and the events' severities per bucket of ``bucket_seconds`` and names the first
+        error line and the first and last event with their times. ValueError when the log spans
+        more than ``max_buckets`` buckets. ``Engine.timeline_bytes``; ``golden.timeline`` is the
+        specification; the frequency window is not touched."""
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("timeline"):
+            return self.engine.timeline_bytes(logs, bucket_seconds=bucket_seconds, max_buckets=max_buckets)
+
+    def timeline_file(self, path: str, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
+        """``timeline`` of a log file, read as ONE document whatever its size."""
+        with open(path, "rb") as f:
+            return self.timeline(f.read(), bucket_seconds=bucket_seconds, max_buckets=max_buckets)
+
+    def _timeline_accumulator(self, bucket_seconds: int, max_buckets: int):
+        from .timeline import TimelineAccumulator
+        with self._engine_guard("timeline"):
+            return TimelineAccumulator(self.engine, bucket_seconds, max_buckets,
+                                       guard=lambda: self._engine_guard("timeline"))
+
+    def timeline_stream(self, src_or_path, chunk_bytes: Optional[int] = None, bucket_seconds: int = 60,
+                        max_buckets: int = 65536) -> dict:
+        """``timeline`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The report is
+        exactly the one-document report, whatever the chunk size."""
+        if isinstance(src_or_path, (str, os.PathLike)):
+            size = os.path.getsize(src_or_path)
+            with open(src_or_path, "rb") as f:
+                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
+                try:
+                    return self.timeline_stream(mm, chunk_bytes=chunk_bytes, bucket_seconds=bucket_seconds,
+                                                max_buckets=max_buckets)
+                finally:
+                    if size:
+                        mm.close()
+        acc = self._timeline_accumulator(bucket_seconds, max_buckets)
+        acc.add_stream(src_or_path, chunk_bytes)
+        return acc.report()
+
+    def timeline_resident(self, resident, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
+        """``timeline`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        acc = self._timeline_accumulator(bucket_seconds, max_buckets)
+        acc.add_resident(resident)
+        return acc.report()
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

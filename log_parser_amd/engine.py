@@ -888,6 +888,24 @@ class Engine:
                                "example": raw.decode("utf-8", errors="replace")})
         return out
 
+    # ------------------------------------------------------------------ log timeline
+    def timeline_bytes(self, data: bytes, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
+        """When did the lines, the error lines and the events of one document happen?
+        (``golden.timeline`` is the specification.) The stamp at the head of every line is read on
+        the device (csrc/kernels/timeline.hip k_ts_parse), unstamped lines take the time of the
+        nearest earlier stamped line, and lines, error lines, events and severities are counted per
+        bucket of ``bucket_seconds`` (k_tl_hist); only the non-empty buckets come back. ValueError
+        when the document spans more than ``max_buckets`` buckets. Nothing is scored and the
+        frequency window is not touched."""
+        data = bytes(data)
+        text, n = self.stage_text(data)
+        return self.timeline_document(text, n, data, bucket_seconds=bucket_seconds, max_buckets=max_buckets)
+
+    def timeline_document(self, text, n: int, data: bytes, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
+        """``timeline_bytes`` of a staged document: ``text`` = ``stage_text(data)``'s buffer."""
+        from .timeline import timeline_document
+        return timeline_document(self, text, n, data, bucket_seconds, max_buckets)
+
     # documents larger than this are line-indexed on the GPU (k_nl_count/k_nl_write); smaller
     # batches are split on the host while they are being packed (memchr, no extra pass)
     GPU_SPLIT_BYTES = 32 << 20

@@ -27,8 +27,6 @@ With ``cover="events"`` an event covers its own line only and both carries are e
 from __future__ import annotations
 
 import contextlib
-import queue
-import threading
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -37,6 +35,7 @@ import torch
 from .engine import Engine, Segments
 from .golden import line_template
 from .ops import kernels as K
+from .parallel.stream import document_chunks
 
 ORD_SHIFT = 40                      # ordinal = (document << ORD_SHIFT) | line
 ORD_LINE_MASK = (1 << ORD_SHIFT) - 1
@@ -156,70 +155,6 @@ class GapAccumulator:
         self._fold(doc, line, sig, fetch)
 
     # ------------------------------------------------------------------ one document in chunks
-    def _chunks(self, src, chunk_bytes: Optional[int]):
-        """(text, n, left halo lines, right halo lines, host bytes or None) of every chunk of
-        ``src``: a ``ResidentLog``'s chunks as they lie in HBM, or a host source staged by
-        ``StreamAnalyzer._producer`` (pinned buffers, the copy of the next chunk in flight on its
-        own stream). A library with backtracker regexes keeps a chunk's pinned bytes until the
-        chunk is done: the host side path reads them."""
-        from .parallel.stream import ResidentLog, StreamAnalyzer, _eff_end, auto_chunk_bytes
-        eng = self.engine
-        dev = eng.device
-        if isinstance(src, ResidentLog):
-            if src.halo < eng.lib.halo:
-                raise ValueError(f"resident log staged with {src.halo} halo lines, the library needs {eng.lib.halo}")
-            for d, n, lh, rh, _ in src.chunks:
-                yield d, n, lh, rh, None
-            return
-        sa = StreamAnalyzer(eng, chunk_bytes=chunk_bytes, topk=1)
-        eff = _eff_end(src)
-        if eff == 0 and len(src) > 0 and src.find(b"\n", 0) >= 0:
-            return                                      # only line ends: no line (Java's split)
-        if sa._auto_chunk:
-            sa.chunk_bytes = auto_chunk_bytes(dev, eff)
-        cuda = dev.type == "cuda"
-        hold = bool(eng.lib.host_plan)
-        q: "queue.Queue" = queue.Queue(maxsize=2)
-        free_q: Optional[queue.Queue] = None
-        if cuda:
-            free_q = queue.Queue()
-            for _ in range(sa.PINNED_BUFFERS):
-                free_q.put((None, None))
-        copy_stream = torch.cuda.Stream(dev) if cuda else None
-        th = threading.Thread(target=sa._producer, args=(src, eff, q, 0, free_q), daemon=True)
-        th.start()
-
-        def fetch():
-            item = q.get()
-            if isinstance(item, BaseException):
-                raise item
-            if item is None:
-                return None
-            pinned, n, size, lh, rh, _ = item
-            if not cuda:
-                return pinned, n, lh, rh, pinned, None
-            with torch.cuda.stream(copy_stream):
-                d = torch.empty(size, dtype=torch.uint8, device=dev)
-                d.copy_(pinned[:size], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
-            if not hold:
-                free_q.put((pinned, ev))                # recycled once the copy is done
-                pinned = None
-            return d, n, lh, rh, pinned, ev
-
-        nxt = fetch()
-        while nxt is not None:
-            text, n, lh, rh, host, ev = nxt
-            if ev is not None:
-                torch.cuda.current_stream(dev).wait_event(ev)
-                text.record_stream(torch.cuda.current_stream(dev))
-            nxt = fetch()                               # stage + copy the next chunk meanwhile
-            yield text, n, lh, rh, (host if hold else None)
-            if cuda and hold:
-                free_q.put((host, ev))                  # the side path has read the pinned bytes
-        th.join()
-
     def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
         """A bytes-like source (bytes, mmap, ``RepeatBuffer``) as ONE document, in chunks."""
         with self._guard():
@@ -240,7 +175,7 @@ class GapAccumulator:
         line_base = 0                       # global number of the chunk's first own line
         cov_until = 0                       # forward carry
         held: List[tuple] = []              # backward carry: (global line, signature, raw), ascending
-        for text, n, lh, rh, host in self._chunks(src, chunk_bytes):
+        for text, n, lh, rh, host in document_chunks(eng, src, chunk_bytes):
             ls, ll = K.split_chunk_lines(text, n)
             L = ls.numel()
             own_lo, own_hi = lh, L - rh

@@ -26,7 +26,7 @@ import threading
 import time
 import uuid
 from collections import deque
-from datetime import datetime, timezone
+from datetime import datetime, timedelta, timezone
 from typing import Callable, Dict, List, Optional, Sequence
 
 from .models.schema import Pattern, PatternSet, pattern_to_json
@@ -420,3 +420,123 @@ def gaps_corpus(docs, pattern_sets: List[PatternSet], params: ScoringParams, top
             "templates": len(merged), "top": [
                 {**_gap_group_fields(sig, c, i, raw), "documents": nd, "firstDocument": d}
                 for sig, (c, d, i, raw, nd) in order], "documents": len(docs)}
+
+
+# ---------------------------------------------------------------------------------------------
+# Log timeline (an extra: the reference reads no time a log line carries). When did the lines, the
+# error lines and the events of a log happen? These functions are the specification of
+# ``Engine.timeline_bytes`` and of the timestamp kernel (csrc/kernels/ts_core.h).
+#
+# Not covered: stamps without a year or with month names (klog ``E0919 12:00:00``, syslog
+# ``Sep 19 12:00:00``, Apache ``19/Sep/2025:12:00:00``) and bare epoch numbers.
+
+TS_MAX_START = 32
+_STAMP = re.compile(rb"(?<![0-9A-Za-z])(\d{4})[-/](\d\d)[-/](\d\d)[T ](\d\d):(\d\d):(\d\d)"
+                    rb"(?:[.,](\d{1,9}))?(Z|[+-]\d\d:?\d\d)?")
+_EPOCH = datetime(1970, 1, 1, tzinfo=timezone.utc)
+
+
+def line_timestamp(line: bytes) -> Optional[int]:
+    """Epoch milliseconds (UTC) of the stamp at the head of ``line``, or None: the leftmost match
+    of the grammar, which must start before byte ``TS_MAX_START`` and hold valid fields (year >=
+    1970, Gregorian month lengths, zone hour <= 23) -- later positions are not tried. The fraction
+    is truncated to milliseconds; no zone and ``Z`` mean UTC, ``+hh:mm`` / ``+hhmm`` is subtracted."""
+    m = _STAMP.search(bytes(line))
+    if m is None or m.start() >= TS_MAX_START:
+        return None
+    y, mo, d, h, mi, s = (int(m.group(k)) for k in range(1, 7))
+    if y < 1970 or h > 23 or mi > 59 or s > 59:
+        return None
+    try:
+        t = datetime(y, mo, d, h, mi, s, tzinfo=timezone.utc)
+    except ValueError:                                      # month 13, February 30, ...
+        return None
+    ms = (t - _EPOCH) // timedelta(milliseconds=1)
+    if m.group(7):
+        ms += int(m.group(7)[:3].ljust(3, b"0"))
+    z = m.group(8)
+    if z and z != b"Z":
+        zh, zm = int(z[1:3]), int(z[-2:])
+        if zh > 23 or zm > 59:
+            return None
+        ms -= (-1 if z[:1] == b"-" else 1) * (zh * 60 + zm) * 60000
+    return ms
+
+
+def iso_ms(t: int) -> str:
+    """``YYYY-MM-DDTHH:MM:SS.mmmZ`` of epoch milliseconds."""
+    d = _EPOCH + timedelta(milliseconds=t)
+    return "%04d-%02d-%02dT%02d:%02d:%02d.%03dZ" % (d.year, d.month, d.day, d.hour, d.minute, d.second,
+                                                    d.microsecond // 1000)
+
+
+def timeline_span_error(first: int, last: int, W: int, max_buckets: int) -> ValueError:
+    """The error of a document whose first and last bucket (starts ``first`` / ``last``) are more
+    than ``max_buckets`` buckets apart."""
+    return ValueError("timeline: the log spans %d buckets of %g s (%s .. %s), more than max_buckets=%d; "
+                      "use a larger bucket" % ((last - first) // W + 1, W / 1000, iso_ms(first), iso_ms(last),
+                                               max_buckets))
+
+
+def timeline(logs, pattern_sets: List[PatternSet], params: ScoringParams, bucket_seconds: int = 60,
+             max_buckets: int = 65536) -> dict:
+    """The timeline report of one document. A line's effective time is its own stamp
+    (``line_timestamp``), else the stamp of the nearest earlier stamped line; lines before the first
+    stamped line are undated. Lines, error lines (``gap_candidate``), events (``analyze``) and the
+    events' severities are counted per bucket of ``bucket_seconds``, aligned to multiples of it."""
+    if isinstance(bucket_seconds, bool) or not isinstance(bucket_seconds, int) or bucket_seconds < 1:
+        raise ValueError("timeline: bucket_seconds must be an integer >= 1")
+    if isinstance(logs, (bytes, bytearray, memoryview)):
+        logs = bytes(logs).decode("utf-8", errors="surrogateescape")
+    res = analyze(logs, pattern_sets, params, FrequencyTracker(params))
+    lines = split_lines(logs)
+    W = 1000 * bucket_seconds
+    own = [line_timestamp(l.encode("utf-8", errors="surrogateescape")) for l in lines]
+    eff: List[Optional[int]] = []
+    cur = top = None
+    out_of_order = 0
+    for t in own:
+        if t is not None:
+            if top is not None and t < top:
+                out_of_order += 1
+            top = t if top is None else max(top, t)
+            cur = t
+        eff.append(cur)
+    stamps = [t for t in own if t is not None]
+    events = res["events"]
+    out = {"totalLines": len(lines), "stampedLines": len(stamps), "undatedLines": sum(t is None for t in eff),
+           "outOfOrderLines": out_of_order,
+           "firstTimestamp": iso_ms(min(stamps)) if stamps else None,
+           "lastTimestamp": iso_ms(max(stamps)) if stamps else None,
+           "bucketSeconds": bucket_seconds, "events": len(events),
+           "undatedEvents": sum(eff[e["lineNumber"] - 1] is None for e in events),
+           "firstErrorLine": None, "firstEvent": None, "lastEvent": None, "buckets": []}
+    if not stamps:
+        return out
+    first, last = min(stamps) // W * W, max(stamps) // W * W
+    if (last - first) // W + 1 > max_buckets:
+        raise timeline_span_error(first, last, W, max_buckets)
+    buckets: Dict[int, dict] = {}
+    for i, line in enumerate(lines):
+        if eff[i] is None:
+            continue
+        b = buckets.setdefault(eff[i] // W * W, {"lines": 0, "errorLines": 0, "events": 0, "severity": {}})
+        b["lines"] += 1
+        if gap_candidate(line):
+            b["errorLines"] += 1
+            if out["firstErrorLine"] is None:
+                out["firstErrorLine"] = {"lineNumber": i + 1, "timestamp": iso_ms(eff[i])}
+    for e in events:
+        t = eff[e["lineNumber"] - 1]
+        if t is None:
+            continue
+        b = buckets[t // W * W]
+        b["events"] += 1
+        s = severity_key(e["matchedPattern"].get("severity"))
+        b["severity"][s] = b["severity"].get(s, 0) + 1
+        ref = {"lineNumber": e["lineNumber"], "patternId": e["matchedPattern"].get("id"), "timestamp": iso_ms(t)}
+        if out["firstEvent"] is None:
+            out["firstEvent"] = ref
+        out["lastEvent"] = ref
+    out["buckets"] = [{"start": iso_ms(t), **buckets[t]} for t in sorted(buckets)]
+    return out

@@ -1015,3 +1015,76 @@ class GapTable:
         cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
         N.gap_winners(tab, sig.data_ptr(), ord.data_ptr(), n, out.data_ptr(), cnt.data_ptr(), st, self._cuda)
         return out[:int(cnt.item())]
+
+
+# ---------------------------------------------------------------------------------------------
+# log timeline (csrc/kernels/timeline.hip): the timestamp of every line, counts per time bucket
+
+TS_NONE = -(1 << 63)        # a line without a stamp / without an effective time (csrc/kernels/ts_core.h)
+TL_TILE = 2048              # items (lines, then events) per block of k_tl_hist
+TL_LDS_SLOTS = 256          # buckets of its block table at most: more distinct buckets in a tile go to HBM directly
+
+
+def line_timestamps(text, line_start, line_len) -> torch.Tensor:
+    """Epoch milliseconds (UTC) of the stamp at the head of every line (int64[L], ``TS_NONE``
+    where a line has none; ``golden.line_timestamp``): k_ts_parse or its host twin."""
+    L = line_start.numel()
+    if line_start.dtype != torch.int64 or not line_start.is_contiguous():
+        raise ValueError("line_timestamps: line_start must be contiguous int64[L]")
+    if line_len.dtype != torch.int32 or line_len.numel() != L or not line_len.is_contiguous():
+        raise ValueError("line_timestamps: line_len must be contiguous int32[L]")
+    if text.dtype != torch.uint8 or not text.is_contiguous() or line_start.device != text.device \
+            or line_len.device != text.device:
+        raise ValueError("line_timestamps: text must be contiguous uint8, the line index on its device")
+    out = torch.empty(L, dtype=torch.int64, device=text.device)
+    if L:
+        N.ts_parse(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, out.data_ptr(),
+                   _s(text), text.is_cuda)
+    return out
+
+
+def timeline_fill(ts: torch.Tensor, carry_last: int = TS_NONE,
+                  carry_top: int = TS_NONE) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Effective times and the out-of-order count of the stamps ``ts`` (int64[L], line order):
+    (eff int64[L], count int64[1] on the device). ``eff[i]`` is the stamp of the nearest stamped
+    line at or before i -- the nearest, not the largest -- else ``carry_last``; a stamped line
+    counts as out of order when its stamp is below the largest stamp before it (``carry_top``
+    included). The carries continue the scans across the chunks of a stream. k_tl_tiles /
+    k_tl_prefix / k_tl_fill or their host twin."""
+    if ts.dtype != torch.int64 or not ts.is_contiguous():
+        raise ValueError("timeline_fill: ts must be contiguous int64[L]")
+    L = ts.numel()
+    eff = torch.empty_like(ts)
+    ooo = torch.zeros(1, dtype=torch.int64, device=ts.device)
+    if L:
+        tmp = torch.empty(N.tl_fill_tmp_words(L), dtype=torch.int64, device=ts.device) if ts.is_cuda else None
+        N.tl_fill(ts.data_ptr(), L, int(carry_last), int(carry_top), eff.data_ptr(), ooo.data_ptr(), _p(tmp), _s(ts),
+                  ts.is_cuda)
+    return eff, ooo
+
+
+def timeline_hist(eff: torch.Tensor, feat: torch.Tensor, ev_line: torch.Tensor, ev_pat: torch.Tensor,
+                  sev_index: torch.Tensor, t0: int, W: int, nb: int, S: int) -> torch.Tensor:
+    """int64[nb, 3 + S]: per bucket ``[t0 + b * W, t0 + (b + 1) * W)`` the lines whose effective
+    time ``eff`` (int64[L], ``TS_NONE``: undated) falls into it, those of them that are error
+    lines (``feat``: uint8[L] context features), the events on them (``ev_line`` / ``ev_pat``:
+    int32[E]) and these per severity (``sev_index``: int32[P]). Undated lines and events, and
+    times outside the nb buckets, are counted nowhere. k_tl_hist or its host twin."""
+    dev = eff.device
+    L, E = eff.numel(), ev_line.numel()
+    if eff.dtype != torch.int64 or not eff.is_contiguous():
+        raise ValueError("timeline_hist: eff must be contiguous int64[L]")
+    if feat.dtype != torch.uint8 or feat.numel() < L or not feat.is_contiguous():
+        raise ValueError("timeline_hist: feat must be contiguous uint8[L]")
+    if ev_pat.numel() != E:
+        raise ValueError("timeline_hist: ev_line and ev_pat differ in length")
+    if W < 1 or not 1 <= nb < (1 << 31) or S < 0:
+        raise ValueError("timeline_hist: need W >= 1, 1 <= nb < 2^31, S >= 0")
+    ev_line = ev_line.to(device=dev, dtype=torch.int32).contiguous()
+    ev_pat = ev_pat.to(device=dev, dtype=torch.int32).contiguous()
+    sev_index = sev_index.to(device=dev, dtype=torch.int32).contiguous()
+    hist = torch.zeros((nb, 3 + S), dtype=torch.int64, device=dev)
+    if L + E:
+        N.tl_hist(eff.data_ptr(), feat.data_ptr(), L, ev_line.data_ptr(), ev_pat.data_ptr(), E, sev_index.data_ptr(),
+                  sev_index.numel(), S, int(t0), int(W), int(nb), hist.data_ptr(), _s(eff), eff.is_cuda)
+    return hist

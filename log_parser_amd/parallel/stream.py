@@ -635,6 +635,95 @@ class StreamAnalyzer:
         return out
 
 
+def document_chunks(eng: Engine, src, chunk_bytes: Optional[int]):
+    """(text, n, left halo lines, right halo lines, host bytes or None) of every chunk of ``src``
+    as ONE document, for the reports that walk a log without scoring it (gapreport.py,
+    timeline.py): a ``ResidentLog``'s chunks as they lie in HBM, or a host source staged by
+    ``StreamAnalyzer._producer`` (pinned buffers, the copy of the next chunk in flight on its
+    own stream). A library with backtracker regexes keeps a chunk's pinned bytes until the
+    chunk is done: the host side path reads them.
+
+    A consumer that may stop early (an exception in the middle of the log) closes the generator
+    (``contextlib.closing``): the producer thread is then told to stop after the chunk it is
+    staging, what it has queued is taken off, and it is joined, so nothing holds on to ``src`` (an
+    mmap can be closed) and no thread or pinned buffer is left behind."""
+    dev = eng.device
+    if isinstance(src, ResidentLog):
+        if src.halo < eng.lib.halo:
+            raise ValueError(f"resident log staged with {src.halo} halo lines, the library needs {eng.lib.halo}")
+        for d, n, lh, rh, _ in src.chunks:
+            yield d, n, lh, rh, None
+        return
+    sa = StreamAnalyzer(eng, chunk_bytes=chunk_bytes, topk=1)
+    eff = _eff_end(src)
+    if eff == 0 and len(src) > 0 and src.find(b"\n", 0) >= 0:
+        return                                      # only line ends: no line (Java's split)
+    if sa._auto_chunk:
+        sa.chunk_bytes = auto_chunk_bytes(dev, eff)
+    cuda = dev.type == "cuda"
+    hold = bool(eng.lib.host_plan)
+    q: "queue.Queue" = queue.Queue(maxsize=2)
+    free_q: Optional[queue.Queue] = None
+    if cuda:
+        free_q = queue.Queue()
+        for _ in range(sa.PINNED_BUFFERS):
+            free_q.put((None, None))
+    copy_stream = torch.cuda.Stream(dev) if cuda else None
+    stop = threading.Event()
+    ended = False                                   # the producer's last item (None or its exception) is taken
+
+    def plan():                                     # the chunk plan, cut short once the consumer has stopped
+        for ent in sa._plan(src, eff, 0):
+            if stop.is_set():
+                return
+            yield ent
+
+    th = threading.Thread(target=sa._producer, args=(src, eff, q, 0, free_q, plan()), daemon=True)
+    th.start()
+
+    def fetch():
+        nonlocal ended
+        item = q.get()
+        if item is None or isinstance(item, BaseException):
+            ended = True
+        if isinstance(item, BaseException):
+            raise item
+        if item is None:
+            return None
+        pinned, n, size, lh, rh, _ = item
+        if not cuda:
+            return pinned, n, lh, rh, pinned, None
+        with torch.cuda.stream(copy_stream):
+            d = torch.empty(size, dtype=torch.uint8, device=dev)
+            d.copy_(pinned[:size], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(copy_stream)
+        if not hold:
+            free_q.put((pinned, ev))                # recycled once the copy is done
+            pinned = None
+        return d, n, lh, rh, pinned, ev
+
+    try:
+        nxt = fetch()
+        while nxt is not None:
+            text, n, lh, rh, host, ev = nxt
+            if ev is not None:
+                torch.cuda.current_stream(dev).wait_event(ev)
+                text.record_stream(torch.cuda.current_stream(dev))
+            nxt = fetch()                           # stage + copy the next chunk meanwhile
+            yield text, n, lh, rh, (host if hold else None)
+            if cuda and hold:
+                free_q.put((host, ev))              # the side path has read the pinned bytes
+    finally:
+        stop.set()
+        if free_q is not None:                      # (the producer may be waiting for a buffer the consumer holds)
+            free_q.put((None, None))
+        while not ended:                            # unblock its q.put until it has said it is done
+            item = q.get()
+            ended = item is None or isinstance(item, BaseException)
+        th.join()
+
+
 class ShardedStreamAnalyzer:
     """One long log streamed over the ranks of a process group (one process per GPU): the chunk
     plan of ``StreamAnalyzer`` is cut into steps of ``world`` consecutive chunks, rank r analyses
