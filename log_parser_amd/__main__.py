@@ -44,13 +44,23 @@ def cmd_validate(args, cfg: Config) -> int:
     return 1 if any(p["kind"] == "invalid" for p in rep["problems"]) else 0
 
 
-def cmd_analyze(args, cfg: Config) -> int:
+def _parser(args, cfg: Config):
+    """The parser of a command that takes ``--patterns`` / ``--device`` (``_library_options``)."""
     from .api import LogParser
     if args.patterns:
         cfg = cfg.replace({"pattern.directory": args.patterns})
     if args.device:
         cfg = cfg.replace({"engine.device": args.device})
-    lp = LogParser.from_directory(cfg["pattern.directory"], config=cfg)
+    return LogParser.from_directory(cfg["pattern.directory"], config=cfg)
+
+
+def _library_options(sub) -> None:
+    sub.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
+    sub.add_argument("--device", help="cuda | cpu | auto")
+
+
+def cmd_analyze(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
     out = lp.parse_file(args.file, stream=True if args.stream else None, topk=args.topk, raw=True)
     if isinstance(out, (bytes, bytearray)):
         sys.stdout.buffer.write(out)
@@ -65,12 +75,7 @@ def cmd_analyze(args, cfg: Config) -> int:
 
 
 def cmd_gaps(args, cfg: Config) -> int:
-    from .api import LogParser
-    if args.patterns:
-        cfg = cfg.replace({"pattern.directory": args.patterns})
-    if args.device:
-        cfg = cfg.replace({"engine.device": args.device})
-    lp = LogParser.from_directory(cfg["pattern.directory"], config=cfg)
+    lp = _parser(args, cfg)
     if len(args.file) > 1:
         if args.stream:
             print("gaps: --stream takes one file", file=sys.stderr)
@@ -90,12 +95,7 @@ def cmd_gaps(args, cfg: Config) -> int:
 
 
 def cmd_timeline(args, cfg: Config) -> int:
-    from .api import LogParser
-    if args.patterns:
-        cfg = cfg.replace({"pattern.directory": args.patterns})
-    if args.device:
-        cfg = cfg.replace({"engine.device": args.device})
-    lp = LogParser.from_directory(cfg["pattern.directory"], config=cfg)
+    lp = _parser(args, cfg)
     call = lp.timeline_stream if args.stream else lp.timeline_file
     try:
         rep = call(args.file, bucket_seconds=args.bucket)
@@ -121,8 +121,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     sub.add_parser("serve", help="run the REST service")
     a = sub.add_parser("analyze", help="analyse a log file")
     a.add_argument("file")
-    a.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
-    a.add_argument("--device", help="cuda | cpu | auto")
+    _library_options(a)
     a.add_argument("--stream", action="store_true", help="chunked streaming pass (automatic for big files)")
     a.add_argument("--topk", type=int, default=20)
     v = sub.add_parser("validate", help="compile a pattern library and report problem regexes")
@@ -130,16 +129,14 @@ def main(argv: Optional[List[str]] = None) -> int:
     v.add_argument("--allow", default="nfa", help="comma list of non-DFA kinds not reported (default nfa)")
     g = sub.add_parser("gaps", help="error lines of a log file that no pattern explains, grouped by template")
     g.add_argument("file", nargs="+", help="one log file, or several: the corpus report in argument order")
-    g.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
-    g.add_argument("--device", help="cuda | cpu | auto")
+    _library_options(g)
     g.add_argument("--stream", action="store_true", help="one file processed in chunks (same report)")
     g.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
     g.add_argument("--cover", choices=("events", "context"), default="context",
                    help="what an event covers: its own line, or its context window too (default)")
     t = sub.add_parser("timeline", help="lines, error lines and events of a log file per time bucket")
     t.add_argument("file")
-    t.add_argument("--patterns", help="pattern directory (default: pattern.directory)")
-    t.add_argument("--device", help="cuda | cpu | auto")
+    _library_options(t)
     t.add_argument("--bucket", type=int, default=60, metavar="SECONDS", help="bucket width (default 60)")
     t.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
     args = ap.parse_args(rest)

@@ -45,6 +45,19 @@ from .utils.config import Config
 _KIND_NAMES = {KIND_DFA: "dfa", KIND_NFA: "nfa", KIND_FALLBACK: "host-fallback", KIND_INVALID: "invalid"}
 
 
+@contextlib.contextmanager
+def _source(src_or_path):
+    """A bytes-like source as it is; the file at a path as a read-only mmap (``b""`` when it is
+    empty: nothing to map), closed on the way out."""
+    if not isinstance(src_or_path, (str, os.PathLike)):
+        yield src_or_path
+    elif not os.path.getsize(src_or_path):
+        yield b""
+    else:
+        with open(src_or_path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            yield mm
+
+
 class LogParser:
     """``LogParser.from_directory(dir).parse(logs)`` -> AnalysisResult dict."""
 
@@ -107,19 +120,14 @@ class LogParser:
     def parse_file(self, path: str, stream: Optional[bool] = None, topk: int = 20, raw: bool = False):
         """A log file: the AnalysisResult dict (``raw``: its JSON bytes) when it is below the stream
         threshold (or ``stream=False``), else a ``StreamResult`` of an mmap'd chunked pass."""
-        size = os.path.getsize(path)
         if stream is None:
-            stream = size > self.stream_threshold()
-        with open(path, "rb") as f:
-            if not stream:
-                text = f.read().decode("utf-8", errors="surrogateescape")
-                return self.parse_json(text) if raw else self.parse(text)
-            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
-            try:
+            stream = os.path.getsize(path) > self.stream_threshold()
+        if stream:
+            with _source(path) as mm:
                 return self.parse_stream(mm, topk=topk)
-            finally:
-                if size:
-                    mm.close()
+        with open(path, "rb") as f:
+            text = f.read().decode("utf-8", errors="surrogateescape")
+        return self.parse_json(text) if raw else self.parse(text)
 
     def load_resident(self, data, chunk_bytes: Optional[int] = None):
         """Stage ``data`` into HBM once (``parallel.stream.ResidentLog``) for repeated analyses."""
@@ -139,13 +147,9 @@ class LogParser:
         (``cover="events"``) or every event's context window (``"context"``) -- grouped by line
         template, most frequent first (``top=None``: every group). ``Engine.gaps_bytes``; the
         frequency window is not touched."""
-        if self._batcher is not None:
-            raise RuntimeError("gaps: the batcher owns the engine after submit(); use a parser of its own")
         if isinstance(logs, str):
             logs = logs.encode("utf-8", errors="surrogateescape")
-        with self._lock:
-            if self._batcher is not None:
-                raise RuntimeError("gaps: the batcher owns the engine after submit(); use a parser of its own")
+        with self._engine_guard("gaps"):
             return self.engine.gaps_bytes(logs, top=top, cover=cover)
 
     def gaps_file(self, path: str, top: Optional[int] = 20, cover: str = "context") -> dict:
@@ -178,17 +182,9 @@ class LogParser:
         """``gaps`` of ONE large log processed in line-aligned chunks with halos (the chunks of
         ``parse_stream``): a bytes-like source, or the path of a file (mmap'd as ``parse_file``
         does). The report is exactly the one-document report, whatever the chunk size."""
-        if isinstance(src_or_path, (str, os.PathLike)):
-            size = os.path.getsize(src_or_path)
-            with open(src_or_path, "rb") as f:
-                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
-                try:
-                    return self.gaps_stream(mm, chunk_bytes=chunk_bytes, top=top, cover=cover)
-                finally:
-                    if size:
-                        mm.close()
         acc = self.gap_accumulator(cover)
-        acc.add_stream(src_or_path, chunk_bytes)
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
         return acc.report(top)
 
     def gaps_resident(self, resident, top: Optional[int] = 20, cover: str = "context") -> dict:
@@ -237,18 +233,9 @@ class LogParser:
         """``timeline`` of ONE large log processed in line-aligned chunks (the chunks of
         ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The report is
         exactly the one-document report, whatever the chunk size."""
-        if isinstance(src_or_path, (str, os.PathLike)):
-            size = os.path.getsize(src_or_path)
-            with open(src_or_path, "rb") as f:
-                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
-                try:
-                    return self.timeline_stream(mm, chunk_bytes=chunk_bytes, bucket_seconds=bucket_seconds,
-                                                max_buckets=max_buckets)
-                finally:
-                    if size:
-                        mm.close()
         acc = self._timeline_accumulator(bucket_seconds, max_buckets)
-        acc.add_stream(src_or_path, chunk_bytes)
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
         return acc.report()
 
     def timeline_resident(self, resident, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:

@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from .frequency import DeviceFrequencyState, FrequencyState
-from .golden import SEVERITY_ORDER, line_template
+from .golden import SEVERITY_ORDER
 from .models.compiled import CompiledLibrary
 from .native import N, host_thread_budget
 from .ops import kernels as K
@@ -816,87 +816,26 @@ class Engine:
         return res, ls, ll
 
     # ------------------------------------------------------------------ coverage-gap report
-    def _gap_coverage(self, ev_line, ev_pat, L: int, cover: str) -> Optional[torch.Tensor]:
-        """uint8[L]: line is an event's line (``cover="events"``) or inside an event's context
-        window (``"context"``; csrc/kernels/post_core.h event_window) -- a difference array."""
-        if ev_line.numel() == 0:
-            return None
-        x = ev_line.long()
-        a, b = x, x + 1
-        if cover == "context":
-            p = ev_pat.long()
-            before, after = self.tabs["ctx_before"][p].long(), self.tabs["ctx_after"][p].long()
-            rules = before >= 0                     # -1: a pattern without context rules covers its line only
-            a = torch.where(rules, (x - before).clamp(min=0), x)
-            b = torch.where(rules, (x + 1 + after).clamp(max=L), x + 1)
-        one = torch.ones_like(x, dtype=torch.int32)
-        diff = torch.zeros(L + 1, dtype=torch.int32, device=ev_line.device)
-        diff.scatter_add_(0, a, one)
-        diff.scatter_add_(0, b, -one)
-        return (diff[:L].cumsum(0) > 0).to(torch.uint8)
-
     def gaps_bytes(self, data: bytes, top: Optional[int] = 20, cover: str = "context") -> dict:
         """Which error lines of one document does the library not explain, grouped by shape?
-        (``golden.gaps`` is the specification.) The document is matched as ``analyze_bytes`` does,
-        every line is classified by the context DFAs, and the candidate lines outside every event
-        (``cover="events"``) or every event's context window (``"context"``) are grouped by
-        template signature (csrc/kernels/gaps.hip) -- integer tensor work on the device; only the
-        ``top`` groups' numbers come back, and the host renders their template and example from
-        its copy of the text. Nothing is scored and the frequency window is not touched."""
-        if cover not in ("events", "context"):
-            raise ValueError("cover must be 'events' or 'context'")
+        (gapreport.py; ``golden.gaps`` is the specification.) Candidate lines outside every event
+        (``cover="events"``) or every event's context window (``"context"``), the ``top`` groups.
+        Nothing is scored and the frequency window is not touched."""
         data = bytes(data)
         text, n = self.stage_text(data)
         return self.gaps_document(text, n, data, top=top, cover=cover)
 
     def gaps_document(self, text, n: int, data: bytes, top: Optional[int] = 20, cover: str = "context") -> dict:
         """``gaps_bytes`` of a staged document: ``text`` = ``stage_text(data)``'s buffer."""
-        if cover not in ("events", "context"):
-            raise ValueError("cover must be 'events' or 'context'")
-        ls, ll = K.split_lines(text, n)
-        L = ls.numel()
-        out = {"totalLines": L, "events": 0, "errorLines": 0, "uncoveredErrorLines": 0, "templates": 0, "top": []}
-        if L == 0:
-            return out
-        segs = Segments.single(L, self.device)
-        prep = self.prepare(text, n, ls, ll, segs, np.frombuffer(data, np.uint8) if n else None)
-        out["events"] = int(prep.ev_line.numel())
-        feat = K.context_features_all(text, ls, ll, self.tabs["dfa"], self.lib.ctx_dfa_extent)
-        cov = self._gap_coverage(prep.ev_line, prep.ev_pat, L, cover)
-        # (capacity L: 12 bytes per line next to the text's ~100, and never a second run)
-        line, sig, n_cand = K.gap_lines(text, ls, ll, feat, cov, L)
-        out["errorLines"], out["uncoveredErrorLines"] = int(n_cand), int(line.numel())
-        if line.numel() == 0:
-            return out
-        # groups: stable sort by line, then by signature -> runs of one signature in line order
-        line, o = torch.sort(line.long(), stable=True)
-        sig, o2 = torch.sort(sig[o], stable=True)
-        line = line[o2]
-        usig, counts = torch.unique_consecutive(sig, return_counts=True)
-        first = line[counts.cumsum(0) - counts]                 # each group's head = its first line
-        order = torch.sort(first, stable=True)[1]               # by (-count, first line)
-        order = order[torch.sort(counts[order], descending=True, stable=True)[1]]
-        out["templates"] = int(usig.numel())
-        if top is not None:
-            order = order[:max(0, int(top))]
-        f = first[order]
-        rows = torch.stack([counts[order], f, usig[order], ls[f], ll[f].long()]).cpu().tolist()
-        for c, x, s, a, m in zip(*rows):
-            raw = data[a:a + m]
-            out["top"].append({"count": c, "firstLine": x + 1, "signature": "%016x" % (s & 0xFFFFFFFFFFFFFFFF),
-                               "template": line_template(raw).decode("utf-8", errors="replace"),
-                               "example": raw.decode("utf-8", errors="replace")})
-        return out
+        from .gapreport import gaps_document
+        return gaps_document(self, text, n, data, top, cover)
 
     # ------------------------------------------------------------------ log timeline
     def timeline_bytes(self, data: bytes, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
         """When did the lines, the error lines and the events of one document happen?
-        (``golden.timeline`` is the specification.) The stamp at the head of every line is read on
-        the device (csrc/kernels/timeline.hip k_ts_parse), unstamped lines take the time of the
-        nearest earlier stamped line, and lines, error lines, events and severities are counted per
-        bucket of ``bucket_seconds`` (k_tl_hist); only the non-empty buckets come back. ValueError
-        when the document spans more than ``max_buckets`` buckets. Nothing is scored and the
-        frequency window is not touched."""
+        (timeline.py; ``golden.timeline`` is the specification.) Counts per bucket of
+        ``bucket_seconds``, only the non-empty buckets; ValueError when the document spans more than
+        ``max_buckets`` buckets. Nothing is scored and the frequency window is not touched."""
         data = bytes(data)
         text, n = self.stage_text(data)
         return self.timeline_document(text, n, data, bucket_seconds=bucket_seconds, max_buckets=max_buckets)

@@ -1,59 +1,114 @@
-"""Coverage-gap report beyond one document: a stream in chunks, a log resident in HBM, a corpus
-of documents (``golden.gaps`` / ``golden.gaps_corpus`` are the specification).
+"""Coverage-gap report: which error lines of a log does the library not explain, grouped by
+shape? One document, a stream in chunks, a log resident in HBM, a corpus of documents
+(``golden.gaps`` / ``golden.gaps_corpus`` are the specification).
 
-``Engine.gaps_document`` groups one document's (line, signature) pairs with sorts, which a second
-chunk or document cannot continue. :class:`GapAccumulator` folds the pairs of every launch into a
-device-resident ``GapTable`` (csrc/kernels/gap_table.hip) instead: per signature its count, its
-smallest *ordinal* ``(document << 40) | line`` and the number of documents it occurs in. After each
-fold the kernel names the pairs that hold their group's smallest ordinal; only those lines' text
-comes to the host, as the group's example.
+A source is walked in pieces (pieces.py). Every line of a piece is classified by the context DFAs,
+and the candidate lines outside every event (``cover="events"``) or every event's context window
+(``"context"``) get a template signature (csrc/kernels/gaps.hip) -- all on the device.
 
-A stream (or a ``ResidentLog``) is ONE document processed in the chunks of ``StreamAnalyzer``
-(``_plan`` / ``_producer``: line-aligned, with halos). ``Engine.prepare`` emits the events of a
-chunk's own lines only, so an event of a neighbouring chunk can cover a line of this one. Context
-windows are contiguous and at most ``lib.halo`` lines wide; two carries make the result exact for
-every chunk size:
+:func:`gaps_document` (``Engine.gaps_document``) groups one document's (line, signature) pairs
+with sorts, which a second piece or document cannot continue. :class:`GapAccumulator` folds the
+pairs of every piece into a device-resident ``GapTable`` (csrc/kernels/gap_table.hip) instead: per
+signature its count, its smallest *ordinal* ``(document << 40) | line`` and the number of documents
+it occurs in. After each fold the kernel names the pairs that hold their group's smallest ordinal;
+only those lines' text comes to the host, as the group's example.
 
-* forward: ``cov_until``, the largest global window end of any event of the earlier chunks -- an
+A piece carries the events of its own lines only, so an event of a neighbouring piece can cover a
+line of this one. Context windows are contiguous and at most ``lib.halo`` lines wide; two carries
+make the result exact for every chunk size:
+
+* forward: ``cov_until``, the largest global window end of any event of the earlier pieces -- an
   own candidate with global line ``g < cov_until`` is covered;
-* backward: an uncovered candidate within ``max(lines_before)`` lines of its chunk's end is held
-  back (global line, signature, text). Once a later chunk's events are known, held lines at or
-  after that chunk's smallest window start are dropped as covered; held lines no later event can
-  reach (``g + max_before`` < the next chunk's first line) are folded; the rest stay held -- a
-  chunk can be a single line -- and the end of the source folds what remains.
+* backward: an uncovered candidate within ``max(lines_before)`` lines of its piece's end is held
+  back (global line, signature, text). Once a later piece's events are known, held lines at or
+  after that piece's smallest window start are dropped as covered; held lines no later event can
+  reach (``g + max_before`` < the next piece's first line) are folded; the rest stay held -- a
+  piece can be a single line -- and the last piece holds nothing back and folds what remains.
 
 With ``cover="events"`` an event covers its own line only and both carries are empty.
 """
 from __future__ import annotations
 
 import contextlib
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from .engine import Engine, Segments
+from .engine import Engine
 from .golden import line_template
 from .ops import kernels as K
-from .parallel.stream import document_chunks
+from .pieces import Piece, document_piece, stream_pieces
 
 ORD_SHIFT = 40                      # ordinal = (document << ORD_SHIFT) | line
 ORD_LINE_MASK = (1 << ORD_SHIFT) - 1
 
 
-def gather_lines(text: torch.Tensor, starts: torch.Tensor, lens: torch.Tensor) -> List[bytes]:
-    """The byte ranges text[starts[i] : starts[i] + lens[i]] as bytes objects: one gather on the
-    text's device and one copy to the host, however many ranges."""
-    lens = lens.long()
-    total = int(lens.sum().item()) if lens.numel() else 0
-    ends = lens.cumsum(0)
-    if total:
-        idx = torch.arange(total, device=text.device) + torch.repeat_interleave(starts.long() - (ends - lens), lens)
-        blob = text[idx].cpu().numpy().tobytes()
-    else:
-        blob = b""
-    ends = ends.tolist()
-    return [blob[a:b] for a, b in zip([0] + ends[:-1], ends)]
+def check_cover(cover: str) -> None:
+    if cover not in ("events", "context"):
+        raise ValueError("cover must be 'events' or 'context'")
+
+
+def event_windows(tabs: dict, ev_line: torch.Tensor, ev_pat: torch.Tensor, cover: str):
+    """(a, b) per event: the lines [a, b) it covers, in ``ev_line``'s numbering and unclamped -- its
+    line (``cover="events"``) or its context window (csrc/kernels/post_core.h event_window)."""
+    x = ev_line.long()
+    if cover != "context":
+        return x, x + 1
+    p = ev_pat.long()
+    before, after = tabs["ctx_before"][p].long(), tabs["ctx_after"][p].long()
+    rules = before >= 0                     # -1: a pattern without context rules covers its line only
+    return torch.where(rules, x - before, x), torch.where(rules, x + 1 + after, x + 1)
+
+
+def coverage(a: torch.Tensor, b: torch.Tensor, L: int) -> Optional[torch.Tensor]:
+    """uint8[L]: line is inside one of the windows [a, b) (clamped to the ``L`` lines) -- a
+    difference array. None without windows."""
+    if a.numel() == 0:
+        return None
+    a, b = a.clamp(min=0), b.clamp(max=L)
+    one = torch.ones_like(a, dtype=torch.int32)
+    diff = torch.zeros(L + 1, dtype=torch.int32, device=a.device)
+    diff.scatter_add_(0, a, one)
+    diff.scatter_add_(0, b, -one)
+    return (diff[:L].cumsum(0) > 0).to(torch.uint8)
+
+
+def gaps_document(eng: Engine, text, n: int, data: bytes, top: Optional[int] = 20, cover: str = "context") -> dict:
+    """The report of a staged document in one piece (``Engine.gaps_document``): only the ``top``
+    groups' numbers come back; the host renders template and example from its copy of the text."""
+    check_cover(cover)
+    piece = document_piece(eng, text, n, data)
+    L = piece.ls.numel()
+    out = {"totalLines": L, "events": int(piece.ev_line.numel()), "errorLines": 0, "uncoveredErrorLines": 0,
+           "templates": 0, "top": []}
+    feat = piece.features()
+    cov = coverage(*event_windows(eng.tabs, piece.ev_line, piece.ev_pat, cover), L)
+    # (capacity L: 12 bytes per line next to the text's ~100, and never a second run)
+    line, sig, n_cand = K.gap_lines(text, piece.ls, piece.ll, feat, cov, L)
+    out["errorLines"], out["uncoveredErrorLines"] = int(n_cand), int(line.numel())
+    if line.numel() == 0:
+        return out
+    # groups: stable sort by line, then by signature -> runs of one signature in line order
+    line, o = torch.sort(line.long(), stable=True)
+    sig, o2 = torch.sort(sig[o], stable=True)
+    line = line[o2]
+    usig, counts = torch.unique_consecutive(sig, return_counts=True)
+    first = line[counts.cumsum(0) - counts]                 # each group's head = its first line
+    order = torch.sort(first, stable=True)[1]               # by (-count, first line)
+    order = order[torch.sort(counts[order], descending=True, stable=True)[1]]
+    out["templates"] = int(usig.numel())
+    if top is not None:
+        order = order[:max(0, int(top))]
+    f = first[order]
+    # (the rows and their lines' index in ONE read, so not ``piece.raw_lines``)
+    rows = torch.stack([counts[order], f, usig[order], piece.ls[f], piece.ll[f].long()]).cpu().tolist()
+    for c, x, s, a, m in zip(*rows):
+        raw = data[a:a + m]
+        out["top"].append({"count": c, "firstLine": x + 1, "signature": "%016x" % (s & 0xFFFFFFFFFFFFFFFF),
+                           "template": line_template(raw).decode("utf-8", errors="replace"),
+                           "example": raw.decode("utf-8", errors="replace")})
+    return out
 
 
 class GapAccumulator:
@@ -66,8 +121,7 @@ class GapAccumulator:
     def __init__(self, engine: Engine, cover: str = "context", guard: Optional[Callable] = None):
         """``guard``: a context manager factory entered around every use of the engine (the
         parser's lock, ``LogParser.gap_accumulator``)."""
-        if cover not in ("events", "context"):
-            raise ValueError("cover must be 'events' or 'context'")
+        check_cover(cover)
         self.engine = engine
         self._guard = guard or contextlib.nullcontext
         self.cover = cover
@@ -78,7 +132,7 @@ class GapAccumulator:
         self._max_before = max(0, int(np.max(before))) if cover == "context" and len(before) else 0
 
     # ------------------------------------------------------------------ folding
-    def _fold(self, doc: int, line: torch.Tensor, sig: torch.Tensor, fetch: Optional[Callable],
+    def _fold(self, doc: int, line: torch.Tensor, sig: torch.Tensor, fetch: Callable,
               held: Optional[List[tuple]] = None) -> None:
         """Fold the pairs (``line``: lines of document ``doc``, int64) and the released ``held``
         lines [(line, signature, raw)] in one launch; ``fetch(idx)`` returns the raw lines of the
@@ -121,117 +175,70 @@ class GapAccumulator:
         self.documents += 1
         return doc
 
-    # ------------------------------------------------------------------ one whole document
+    # ------------------------------------------------------------------ sources
     def add_document(self, data) -> None:
-        """One document (str or bytes) in one piece: ``Engine.gaps_document``'s steps up to the pairs."""
+        """One document (str or bytes) in one piece."""
         if isinstance(data, str):
             data = data.encode("utf-8", errors="surrogateescape")
+        data = bytes(data)
         with self._guard():
-            self._add_document(bytes(data))
+            self._add_pieces([document_piece(self.engine, *self.engine.stage_text(data), data)])
 
-    def _add_document(self, data: bytes) -> None:
-        eng = self.engine
-        doc = self._new_document()
-        text, n = eng.stage_text(data)
-        ls, ll = K.split_lines(text, n)
-        L = ls.numel()
-        if L == 0:
-            return
-        if L > ORD_LINE_MASK:
-            raise ValueError("GapAccumulator: too many lines for the ordinal")
-        self.lines += L
-        segs = Segments.single(L, eng.device)
-        prep = eng.prepare(text, n, ls, ll, segs, np.frombuffer(data, np.uint8) if n else None)
-        self.events += int(prep.ev_line.numel())
-        feat = K.context_features_all(text, ls, ll, eng.tabs["dfa"], eng.lib.ctx_dfa_extent)
-        cov = eng._gap_coverage(prep.ev_line, prep.ev_pat, L, self.cover)
-        line, sig, n_cand = K.gap_lines(text, ls, ll, feat, cov, L)
-        self.error_lines += int(n_cand)
-
-        def fetch(idx):
-            x = line[idx].long()
-            a, m = torch.stack([ls[x], ll[x].long()]).cpu().tolist()
-            return [data[s:s + k] for s, k in zip(a, m)]
-        self._fold(doc, line, sig, fetch)
-
-    # ------------------------------------------------------------------ one document in chunks
     def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
         """A bytes-like source (bytes, mmap, ``RepeatBuffer``) as ONE document, in chunks."""
-        with self._guard():
-            self._add_chunked(src, chunk_bytes)
+        with self._guard(), stream_pieces(self.engine, src, chunk_bytes) as pieces:
+            self._add_pieces(pieces)
 
     def add_resident(self, res) -> None:
         """A ``ResidentLog`` as ONE document, read in place chunk by chunk."""
-        with self._guard():
-            self._add_chunked(res, None)
+        self.add_stream(res)
 
-    def _add_chunked(self, src, chunk_bytes: Optional[int]) -> None:
-        eng = self.engine
-        dev = eng.device
-        tabs = eng.tabs
+    # ------------------------------------------------------------------ one document, piece by piece
+    def _add_pieces(self, pieces: Iterable[Piece]) -> None:
+        """Fold one document from its pieces. The ``last`` piece holds nothing back and releases
+        everything held."""
         doc = self._new_document()
-        context = self.cover == "context"
-        mb = self._max_before
-        line_base = 0                       # global number of the chunk's first own line
         cov_until = 0                       # forward carry
         held: List[tuple] = []              # backward carry: (global line, signature, raw), ascending
-        for text, n, lh, rh, host in document_chunks(eng, src, chunk_bytes):
-            ls, ll = K.split_chunk_lines(text, n)
-            L = ls.numel()
-            own_lo, own_hi = lh, L - rh
-            n_own = own_hi - own_lo
-            if line_base + n_own > ORD_LINE_MASK:
-                raise ValueError("GapAccumulator: too many lines for the ordinal")
-            segs = Segments.scalar(0, L, own_lo, own_hi, line_base - own_lo, 1 << 62, dev)
-            prep = eng.prepare(text, n, ls, ll, segs, host_text=host[:n].numpy() if host is not None else None,
-                               split_trim=False)
-            ne = int(prep.ev_line.numel())
-            self.events += ne
-            cov = eng._gap_coverage(prep.ev_line, prep.ev_pat, L, self.cover)
-            win_lo = win_hi = None          # global [smallest window start, largest window end) of the chunk's events
-            if context and ne:
-                g = prep.ev_line.long() + (line_base - own_lo)
-                p = prep.ev_pat.long()
-                before, after = tabs["ctx_before"][p].long(), tabs["ctx_after"][p].long()
-                rules = before >= 0
-                lo = torch.where(rules, g - before, g).min()
-                hi = torch.where(rules, g + 1 + after, g + 1).max()
-                win_lo, win_hi = torch.stack([lo, hi]).tolist()
-            if held and win_lo is not None:
-                held = [h for h in held if h[0] < win_lo]           # the rest: inside a window of this chunk
-            if cov_until > line_base and n_own:
-                if cov is None:
-                    cov = torch.zeros(L, dtype=torch.uint8, device=dev)
-                cov[own_lo:own_lo + min(cov_until - line_base, n_own)] = 1
-            o_ls, o_ll = ls[own_lo:own_hi], ll[own_lo:own_hi]
-            feat = K.context_features_all(text, o_ls, o_ll, tabs["dfa"], eng.lib.ctx_dfa_extent)
-            line, sig, n_cand = K.gap_lines(text, o_ls, o_ll, feat, None if cov is None else cov[own_lo:own_hi], n_own)
-            self.error_lines += int(n_cand)
-            self.lines += n_own
-            line = line.long()
-            if mb and line.numel():
-                tail = line >= n_own - mb                           # a later chunk's event may still cover these
-                t_line, t_sig = line[tail], sig[tail]
-                if t_line.numel():
-                    o = torch.sort(t_line)[1]
-                    t_line, t_sig = t_line[o], t_sig[o]
-                    raws = gather_lines(text, o_ls[t_line], o_ll[t_line])
-                    held += [(line_base + x, s, raw) for x, s, raw in zip(t_line.tolist(), t_sig.tolist(), raws)]
-                    line, sig = line[~tail], sig[~tail]
-            nxt = line_base + n_own
-            done = [h for h in held if h[0] + mb < nxt]             # out of every later event's reach
-            held = [h for h in held if h[0] + mb >= nxt]
-            rel = line
+        for piece in pieces:
+            cov_until, held = self._add_piece(doc, piece, cov_until, held)
 
-            def fetch(idx, text=text, o_ls=o_ls, o_ll=o_ll, rel=rel):
-                x = rel[idx]
-                return gather_lines(text, o_ls[x], o_ll[x])
-            self._fold(doc, line + line_base, sig, fetch, done)
-            if win_hi is not None:
-                cov_until = max(cov_until, win_hi)
-            line_base = nxt
-        empty = torch.empty(0, dtype=torch.int64, device=dev)
-        self._fold(doc, empty, empty, None, held)
+    def _add_piece(self, doc: int, piece: Piece, cov_until: int, held: List[tuple]):
+        """Fold one piece of document ``doc``: takes and returns the two carries."""
+        n, base, mb = piece.ls.numel(), piece.line_base, self._max_before
+        if base + n > ORD_LINE_MASK:
+            raise ValueError("GapAccumulator: too many lines for the ordinal")
+        self.lines += n
+        self.events += int(piece.ev_line.numel())
+        a, b = event_windows(self.engine.tabs, piece.ev_line, piece.ev_pat, self.cover)
+        cov = coverage(a, b, n)
+        if cov_until > base and n:
+            if cov is None:
+                cov = torch.zeros(n, dtype=torch.uint8, device=self.engine.device)
+            cov[:min(cov_until - base, n)] = 1
+        # the carries: its events' global [smallest window start, largest window end), where a neighbour can care
+        if self.cover == "context" and a.numel() and (held or not piece.last):
+            win_lo, win_hi = (torch.stack([a.min(), b.max()]) + base).tolist()
+            held = [h for h in held if h[0] < win_lo]               # the rest: inside a window of this piece
+            cov_until = max(cov_until, win_hi)
+        # (capacity n: 12 bytes per line next to the text's ~100, and never a second run)
+        line, sig, n_cand = K.gap_lines(piece.text, piece.ls, piece.ll, piece.features(), cov, n)
+        self.error_lines += int(n_cand)
+        line = line.long()
+        if mb and not piece.last and line.numel():
+            tail = line >= n - mb                                   # a later piece's event may still cover these
+            t_line, t_sig = line[tail], sig[tail]
+            if t_line.numel():
+                o = torch.sort(t_line)[1]
+                t_line, t_sig = t_line[o], t_sig[o]
+                raws = piece.raw_lines(t_line)
+                held += [(base + x, s, raw) for x, s, raw in zip(t_line.tolist(), t_sig.tolist(), raws)]
+                line, sig = line[~tail], sig[~tail]
+        nxt = float("inf") if piece.last else base + n              # the first line a later event can lie on
+        done = [h for h in held if h[0] + mb < nxt]                 # out of every later event's reach
+        held = [h for h in held if h[0] + mb >= nxt]
+        self._fold(doc, line + base, sig, lambda idx: piece.raw_lines(line[idx]), done)
+        return cov_until, held
 
     # ------------------------------------------------------------------ the report
     def report(self, top: Optional[int] = 20) -> dict:

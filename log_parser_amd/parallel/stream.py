@@ -636,23 +636,23 @@ class StreamAnalyzer:
 
 
 def document_chunks(eng: Engine, src, chunk_bytes: Optional[int]):
-    """(text, n, left halo lines, right halo lines, host bytes or None) of every chunk of ``src``
-    as ONE document, for the reports that walk a log without scoring it (gapreport.py,
-    timeline.py): a ``ResidentLog``'s chunks as they lie in HBM, or a host source staged by
+    """(text, n, left halo lines, right halo lines, host bytes or None, this is the last chunk) of
+    every chunk of ``src`` as ONE document, for the reports that walk a log without scoring it
+    (pieces.py): a ``ResidentLog``'s chunks as they lie in HBM, or a host source staged by
     ``StreamAnalyzer._producer`` (pinned buffers, the copy of the next chunk in flight on its
     own stream). A library with backtracker regexes keeps a chunk's pinned bytes until the
     chunk is done: the host side path reads them.
 
     A consumer that may stop early (an exception in the middle of the log) closes the generator
-    (``contextlib.closing``): the producer thread is then told to stop after the chunk it is
+    (``pieces.stream_pieces`` does, on every exit): the producer thread is then told to stop after the chunk it is
     staging, what it has queued is taken off, and it is joined, so nothing holds on to ``src`` (an
     mmap can be closed) and no thread or pinned buffer is left behind."""
     dev = eng.device
     if isinstance(src, ResidentLog):
         if src.halo < eng.lib.halo:
             raise ValueError(f"resident log staged with {src.halo} halo lines, the library needs {eng.lib.halo}")
-        for d, n, lh, rh, _ in src.chunks:
-            yield d, n, lh, rh, None
+        for k, (d, n, lh, rh, _) in enumerate(src.chunks):
+            yield d, n, lh, rh, None, k == len(src.chunks) - 1
         return
     sa = StreamAnalyzer(eng, chunk_bytes=chunk_bytes, topk=1)
     eff = _eff_end(src)
@@ -711,7 +711,7 @@ def document_chunks(eng: Engine, src, chunk_bytes: Optional[int]):
                 torch.cuda.current_stream(dev).wait_event(ev)
                 text.record_stream(torch.cuda.current_stream(dev))
             nxt = fetch()                           # stage + copy the next chunk meanwhile
-            yield text, n, lh, rh, (host if hold else None)
+            yield text, n, lh, rh, (host if hold else None), nxt is None
             if cuda and hold:
                 free_q.put((host, ev))              # the side path has read the pinned bytes
     finally:

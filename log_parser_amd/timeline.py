@@ -1,20 +1,19 @@
 """Log timeline: when did the lines, the error lines and the events of a log happen?
 (``golden.timeline`` is the specification.)
 
-A *piece* is a run of consecutive lines of one document: the whole document
-(``Engine.timeline_document``) or the own lines of one stream chunk. :func:`timeline_piece` reads
-the stamp at the head of every line of a piece (k_ts_parse), gives unstamped lines the time of the
-nearest earlier stamped line (k_tl_fill, which also counts the stamps that run backwards), and
-counts lines, error lines, events and the events' severities per time bucket (k_tl_hist) -- all
-on the text's device; the piece's totals and the non-empty rows of its histogram come to the host
-in two small copies.
+A log is walked in pieces (pieces.py): the whole document (``Engine.timeline_document``) or the
+chunks of a stream. :func:`timeline_piece` reads the stamp at the head of every line of a piece
+(k_ts_parse), gives unstamped lines the time of the nearest earlier stamped line (k_tl_fill, which
+also counts the stamps that run backwards), and counts lines, error lines, events and the events'
+severities per time bucket (k_tl_hist) -- all on the text's device; the piece's totals and the
+non-empty rows of its histogram come to the host in two small copies.
 
-:class:`TimelineAccumulator` walks ONE log in the chunks of ``parallel.stream.document_chunks``
-and merges the pieces. Two carries make the report exactly the one-piece report for every chunk
-size: the effective time of the last line so far (the fill of a chunk's leading unstamped lines)
-and the largest stamp so far (``outOfOrderLines``). Every piece builds a dense histogram from its
-own first bucket; buckets are aligned to multiples of the bucket width, so merging the non-empty
-rows by absolute bucket start is exact. Nothing is scored and the frequency window is not touched.
+:class:`TimelineAccumulator` merges the pieces of ONE log. Two carries make the report exactly the
+one-piece report for every chunk size: the effective time of the last line so far (the fill of a
+chunk's leading unstamped lines) and the largest stamp so far (``outOfOrderLines``). Every piece
+builds a dense histogram from its own first bucket; buckets are aligned to multiples of the bucket
+width, so merging the non-empty rows by absolute bucket start is exact. Nothing is scored and the
+frequency window is not touched.
 """
 from __future__ import annotations
 
@@ -24,10 +23,10 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .engine import Engine, Segments
+from .engine import Engine
 from .golden import iso_ms, timeline_span_error
 from .ops import kernels as K
-from .parallel.stream import document_chunks
+from .pieces import Piece, document_piece, stream_pieces
 
 _I64_MAX = (1 << 63) - 1
 
@@ -62,9 +61,9 @@ class TimelineState:
             raise timeline_span_error(first, last, W, self.max_buckets)
 
 
-def timeline_piece(eng: Engine, st: TimelineState, text, ls, ll, ev_line, ev_pat, line_base: int) -> None:
-    """Add the lines ``ls`` / ``ll`` of ``text`` (global numbers from ``line_base``) and their
-    events (``ev_line``: numbers within the piece, in any order) to ``st``."""
+def timeline_piece(eng: Engine, st: TimelineState, piece: Piece) -> None:
+    """Add the lines of ``piece`` and their events (in any order) to ``st``."""
+    text, ls, ll, ev_line, ev_pat = piece.text, piece.ls, piece.ll, piece.ev_line, piece.ev_pat
     n = ls.numel()
     ne = ev_line.numel()
     st.lines += n
@@ -81,7 +80,7 @@ def timeline_piece(eng: Engine, st: TimelineState, text, ls, ll, ev_line, ev_pat
     # order: below the largest stamp of any earlier line -- two scans in line order, one pass
     eff, n_ooo = K.timeline_fill(ts, st.carry_eff, NONE if st.last_ts is None else st.last_ts)
     dated = eff != NONE
-    feat = K.context_features_all(text, ls, ll, eng.tabs["dfa"], eng.lib.ctx_dfa_extent)
+    feat = piece.features()
     cand = ((feat & 9) != 0) & ((feat & 4) == 0) & dated            # golden.gap_candidate on a dated line
     first_cand = torch.where(cand, ar, n).min()
     nums = [stamped.sum(), dated.sum(), n_ooo[0],
@@ -109,10 +108,10 @@ def timeline_piece(eng: Engine, st: TimelineState, text, ls, ll, ev_line, ev_pat
         st.undated_events += ne - n_ev_dated
         if n_ev_dated:
             if st.first_event is None:
-                st.first_event = (line_base + k_lo // P, k_lo % P, t_lo)
-            st.last_event = (line_base + k_hi // P, k_hi % P, t_hi)
+                st.first_event = (piece.line_base + k_lo // P, k_lo % P, t_lo)
+            st.last_event = (piece.line_base + k_hi // P, k_hi % P, t_hi)
     if c_first < n and st.first_error is None:
-        st.first_error = (line_base + c_first, c_time)
+        st.first_error = (piece.line_base + c_first, c_time)
     if not n_dated:
         return
     W = st.W
@@ -155,12 +154,7 @@ def timeline_document(eng: Engine, text, n: int, data: bytes, bucket_seconds: in
                       max_buckets: int = 65536) -> dict:
     """The report of a staged document in one piece (``Engine.timeline_document``)."""
     st = TimelineState(*check_bucket_args(bucket_seconds, max_buckets))
-    ls, ll = K.split_lines(text, n)
-    L = ls.numel()
-    if L:
-        segs = Segments.single(L, eng.device)
-        prep = eng.prepare(text, n, ls, ll, segs, np.frombuffer(data, np.uint8) if n else None)
-        timeline_piece(eng, st, text, ls, ll, prep.ev_line, prep.ev_pat, 0)
+    timeline_piece(eng, st, document_piece(eng, text, n, data))
     return render(eng, st)
 
 
@@ -177,28 +171,14 @@ class TimelineAccumulator:
         self.state = TimelineState(*check_bucket_args(bucket_seconds, max_buckets))
 
     def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard():
-            self._add_chunked(src, chunk_bytes)
+        eng, st = self.engine, self.state
+        # (a further source continues the log: its first line follows the lines so far)
+        with self._guard(), stream_pieces(eng, src, chunk_bytes, line_base=st.lines) as pieces:
+            for piece in pieces:            # (the span error leaves in the middle of the log)
+                timeline_piece(eng, st, piece)
 
     def add_resident(self, res) -> None:
-        with self._guard():
-            self._add_chunked(res, None)
-
-    def _add_chunked(self, src, chunk_bytes: Optional[int]) -> None:
-        eng, st = self.engine, self.state
-        # closing: the span error leaves in the middle of the log, and the chunk producer must not
-        # outlive it (it holds the source, which the caller may be about to unmap)
-        with contextlib.closing(document_chunks(eng, src, chunk_bytes)) as chunks:
-            for text, n, lh, rh, host in chunks:
-                ls, ll = K.split_chunk_lines(text, n)
-                L = ls.numel()
-                own_lo, own_hi = lh, L - rh         # only a chunk's own lines are counted
-                line_base = st.lines
-                segs = Segments.scalar(0, L, own_lo, own_hi, line_base - own_lo, 1 << 62, eng.device)
-                prep = eng.prepare(text, n, ls, ll, segs, host_text=host[:n].numpy() if host is not None else None,
-                                   split_trim=False)
-                timeline_piece(eng, st, text, ls[own_lo:own_hi], ll[own_lo:own_hi], prep.ev_line - own_lo,
-                               prep.ev_pat, line_base)
+        self.add_stream(res)
 
     def report(self) -> dict:
         with self._guard():

@@ -2,17 +2,21 @@
 (log_parser_amd/gapreport.py): a stream in chunks of any size reports exactly what the one-document
 ``gaps`` reports, a corpus reports what ``golden.gaps_corpus`` specifies."""
 import json
+import mmap
 import os
 import random
 import subprocess
 import sys
+import threading
 
 import pytest
+import torch
 
 from log_parser_amd import golden
 from log_parser_amd.api import LogParser
 from log_parser_amd.models.schema import PatternSet
 from log_parser_amd.parallel.stream import StreamAnalyzer, _eff_end
+from log_parser_amd.pieces import document_piece, gather_lines, stream_pieces
 from log_parser_amd.utils.config import Config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,6 +163,55 @@ def test_stream_from_a_path(parser, tmp_path):
     e = tmp_path / "empty.log"
     e.write_bytes(b"")
     assert parser.gaps_stream(str(e)) == parser.gaps(b"")
+
+
+# ---- 4b. the walker itself (log_parser_amd/pieces.py)
+
+def test_walker_leaves_nothing_behind(parser, tmp_path):
+    """``stream_pieces`` over a mapped file with more chunks than the producer's queue holds, left
+    by an exception after the second piece, by ``break`` there, and at its end: no producer thread
+    stays behind and the mapping can be closed (no exported buffer is left). Exactly the final
+    piece is ``last`` and the pieces' line numbers add up to the document's."""
+    doc = ("2025-09-19T12:00:00Z INFO a\n" + "INFO filler\n" * 40 + "1999-01-01T00:00:00Z ERROR a stray old date\n"
+           + "INFO filler\n" * 400 + "2025-09-19T12:00:01Z INFO b\n")
+    f = tmp_path / "stray.log"
+    f.write_text(doc)
+    threads = threading.active_count()
+    for how in ("raise", "break", "end"):
+        with open(f, "rb") as fh:
+            mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+            seen = []
+            try:
+                with stream_pieces(parser.engine, mm, 64) as pieces:
+                    for piece in pieces:
+                        seen.append((piece.line_base, piece.ls.numel(), piece.last))
+                        if len(seen) == 2 and how == "raise":
+                            raise KeyError("leave in the middle")
+                        if len(seen) == 2 and how == "break":
+                            break
+            except KeyError:
+                assert how == "raise"
+            assert threading.active_count() == threads, how
+            mm.close()                                        # BufferError if the producer's view were alive
+        assert how == "end" or len(seen) == 2
+    assert len(seen) > 8                                      # (the queue holds 2, one more is fetched ahead)
+    assert [last for _, _, last in seen] == [False] * (len(seen) - 1) + [True]
+    at = 0
+    for base, n, _ in seen:
+        assert base == at
+        at += n
+    assert at == len(golden.split_lines(doc)) == 443
+    assert parser.gaps_stream(str(f), chunk_bytes=64) == parser.gaps(doc)
+
+
+def test_raw_lines_host_and_device_agree(parser):
+    """A piece's lines cut from the host bytes == gathered from the staged text."""
+    data = _planted_log().encode()
+    piece = document_piece(parser.engine, *parser.engine.stage_text(data), data)
+    idx = torch.tensor([0, 7, 7, piece.ls.numel() - 1])
+    want = [data.split(b"\n")[i] for i in idx.tolist()]
+    assert piece.raw_lines(idx) == gather_lines(piece.text, piece.ls[idx], piece.ll[idx]) == want
+    assert piece.raw_lines(idx[:0]) == gather_lines(piece.text, piece.ls[:0], piece.ll[:0]) == []
 
 
 # ---- 5. the frequency window is not touched
