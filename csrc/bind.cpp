@@ -1156,6 +1156,36 @@ PYBIND11_MODULE(_lpnative, m) {
     py::gil_scoped_release nogil;
     gap_reinsert_host(T, R, n); },
         py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
+  // ---- novelty report (novelty.hip): the lines whose signature the baseline table does not hold
+  m.def("novel_sig", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, py::tuple tab, uint64_t feat,
+                        uint64_t evm, uint64_t out_line, uint64_t out_sig, uint64_t out_flag, int64_t cap, uint64_t cnt,
+                        uint64_t s, bool dev, int per_block) {
+    NovelSigArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.L = L;
+    A.tab = gt_from(tab);
+    A.feat = P<const uint8_t>(feat); A.evm = P<const uint8_t>(evm);
+    A.out_line = P<int32_t>(out_line); A.out_sig = P<int64_t>(out_sig); A.out_flag = P<uint8_t>(out_flag);
+    A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      novel_sig_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    novel_sig_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("tab"), py::arg("feat"),
+        py::arg("evm"), py::arg("out_line"), py::arg("out_sig"), py::arg("out_flag"), py::arg("cap"), py::arg("cnt"),
+        py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  m.def("gap_contains", [](py::tuple tab, uint64_t sig, int64_t n, uint64_t out, uint64_t s, bool dev) {
+    const GapTab T = gt_from(tab);
+    if (dev) {
+      gap_contains_dev(T, P<const int64_t>(sig), n, P<uint8_t>(out), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    gap_contains_host(T, P<const int64_t>(sig), n, P<uint8_t>(out)); },
+        py::arg("tab"), py::arg("sig"), py::arg("n"), py::arg("out"), py::arg("stream"), py::arg("dev"));
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

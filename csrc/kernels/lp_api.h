@@ -419,6 +419,34 @@ void gap_rows_host(const GapTab& T, const GapRows& R, int64_t out_cap, unsigned 
 void gap_reinsert_host(const GapTab& T, const GapRows& R, int64_t n);
 }  // namespace lp
 
+// ---- novelty report (novelty.hip): the lines whose template signature a baseline table does not hold
+namespace lp {
+struct NovelSigArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t L;
+  GapTab tab;                // the baseline: only read (key column and cap)
+  const uint8_t* feat = nullptr;   // [L] context features of every line, or null: no candidates
+  const uint8_t* evm = nullptr;    // [L] 1 where an event lies on the line, or null
+  // outputs: every line x of [0, L) whose signature is not in `tab`, the first `cap` of them, as
+  // (line, signature bit pattern, flag: bit0 gap_candidate(feat[x]), bit1 evm[x]);
+  // cnt[0] += candidates among all lines, cnt[1] += novel lines (all of them: above cap the caller
+  // re-runs, as with gap_sig_dev), cnt[2] += novel candidates
+  int32_t* out_line; int64_t* out_sig; uint8_t* out_flag;
+  int64_t cap;
+  unsigned long long* cnt;   // [3], zeroed by the caller
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from L.
+// GPU: the triples come in no particular order
+void novel_sig_dev(const NovelSigArgs& A, uint64_t stream, int per_block = 0);
+// appends in line order
+void novel_sig_host(const NovelSigArgs& A);
+// out[i] = 1 when the table holds sig[i] (the signature that equals the empty marker included)
+void gap_contains_dev(const GapTab& T, const int64_t* sig, int64_t n, uint8_t* out, uint64_t stream);
+void gap_contains_host(const GapTab& T, const int64_t* sig, int64_t n, uint8_t* out);
+}  // namespace lp
+
 // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
 namespace lp {
 // out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN

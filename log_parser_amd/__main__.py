@@ -16,6 +16,11 @@
                                                when the lines, error lines and events of a log
                                                happened: the stamps at the head of its lines, counts
                                                per time bucket (JSON); --stream: in chunks (any size)
+  novel     FILE (--baseline FILE [FILE ...] | --baseline-file B.npz) [--save-baseline B.npz]
+            [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--top N]
+            [--order count|first] [--errors-only]
+                                               the lines of a log whose template a baseline of
+                                               healthy logs never showed, grouped by template (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -24,6 +29,7 @@ from __future__ import annotations
 import argparse
 import json
 import logging
+import os
 import sys
 from typing import List, Optional
 
@@ -106,6 +112,34 @@ def cmd_timeline(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_novel(args, cfg: Config) -> int:
+    from .api import _source
+    lp = _parser(args, cfg)
+    try:
+        if args.baseline_file:
+            base = lp.load_baseline(args.baseline_file)
+        else:
+            base = lp.baseline()
+            for path in args.baseline:      # every file one document; big ones in chunks, as parse_file reads them
+                if os.path.getsize(path) > lp.stream_threshold():
+                    with _source(path) as src:
+                        base.add_stream(src)
+                else:
+                    base.add_file(path)
+        if args.save_baseline:
+            base.save(args.save_baseline)
+        kw = {"top": args.top, "order": args.order, "errors_only": args.errors_only}
+        if args.stream:
+            rep = lp.novelty_stream(args.file, base, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.novelty_file(args.file, base, **kw)
+    except ValueError as e:                 # a baseline file of another format
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -139,11 +173,24 @@ def main(argv: Optional[List[str]] = None) -> int:
     _library_options(t)
     t.add_argument("--bucket", type=int, default=60, metavar="SECONDS", help="bucket width (default 60)")
     t.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    n = sub.add_parser("novel", help="lines of a log file whose template a baseline of healthy logs never showed")
+    n.add_argument("file")
+    _library_options(n)
+    src = n.add_mutually_exclusive_group(required=True)
+    src.add_argument("--baseline", nargs="+", metavar="FILE", help="healthy log files, each one document")
+    src.add_argument("--baseline-file", metavar="B.npz", help="a baseline saved by --save-baseline")
+    n.add_argument("--save-baseline", metavar="B.npz", help="write the baseline's signatures to this file")
+    n.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    n.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    n.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
+    n.add_argument("--order", choices=("count", "first"), default="count",
+                   help="most frequent first (default), or in order of first appearance")
+    n.add_argument("--errors-only", action="store_true", help="list only the groups with error lines")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
-            "timeline": cmd_timeline}[args.cmd](args, cfg)
+            "timeline": cmd_timeline, "novel": cmd_novel}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

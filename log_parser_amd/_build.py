@@ -37,6 +37,7 @@ SOURCES = [
     ("kernels/side_path.hip", "hip"),
     ("kernels/gaps.hip", "hip"),
     ("kernels/gap_table.hip", "hip"),
+    ("kernels/novelty.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),

@@ -22,6 +22,9 @@ to embedders, with what an in-process user needs beyond one call at a time:
 * ``timeline`` / ``timeline_file``: when the lines, error lines and events of a log happened --
   the stamps of the lines read on the device, counts per time bucket; ``timeline_stream`` /
   ``timeline_resident`` for one log too large for one piece;
+* ``baseline`` / ``novelty`` / ``novelty_file``: the lines of a log whose template a baseline of
+  healthy logs never showed, grouped by template; ``novelty_stream`` / ``novelty_resident`` for
+  one log too large for one piece;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -243,6 +246,66 @@ class LogParser:
         acc = self._timeline_accumulator(bucket_seconds, max_buckets)
         acc.add_resident(resident)
         return acc.report()
+
+    # ---- novelty report -----------------------------------------------------------------------
+    def baseline(self):
+        """An empty ``novelty.Baseline`` on this parser's device: the template signatures of healthy
+        logs (``add_document`` / ``add_file`` / ``add_stream`` / ``add_resident``, ``save``; each of
+        its calls runs under the batcher guard and the lock of ``novelty``)."""
+        from .novelty import Baseline
+        with self._engine_guard("novelty"):
+            return Baseline(self.engine, guard=lambda: self._engine_guard("novelty"))
+
+    def load_baseline(self, path: str):
+        """The ``novelty.Baseline`` saved at ``path`` (``Baseline.save``), on this parser's device."""
+        from .novelty import Baseline
+        with self._engine_guard("novelty"):
+            return Baseline.load(path, self.engine, guard=lambda: self._engine_guard("novelty"))
+
+    def novelty(self, logs, baseline, top: Optional[int] = 20, order: str = "count", errors_only: bool = False) -> dict:
+        """What does one document (str or bytes) say that the healthy logs of ``baseline`` never
+        said? The lines whose template signature the baseline does not hold, grouped by template:
+        per group its lines, its error lines, the lines an event lies on, its first line and an
+        example. ``order="count"``: most frequent first; ``"first"``: in order of first appearance.
+        ``errors_only`` lists only the groups with error lines (the totals do not change);
+        ``top=None``: every group. ``Engine.novelty_bytes``; ``golden.novelty`` is the
+        specification; the frequency window is not touched."""
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("novelty"):
+            return self.engine.novelty_bytes(logs, baseline, top=top, order=order, errors_only=errors_only)
+
+    def novelty_file(self, path: str, baseline, top: Optional[int] = 20, order: str = "count",
+                     errors_only: bool = False) -> dict:
+        """``novelty`` of a log file, read as ONE document whatever its size."""
+        with open(path, "rb") as f:
+            return self.novelty(f.read(), baseline, top=top, order=order, errors_only=errors_only)
+
+    def _novelty_accumulator(self, baseline):
+        from .novelty import NoveltyAccumulator
+        with self._engine_guard("novelty"):
+            return NoveltyAccumulator(self.engine, baseline, guard=lambda: self._engine_guard("novelty"))
+
+    def novelty_stream(self, src_or_path, baseline, chunk_bytes: Optional[int] = None, top: Optional[int] = 20,
+                       order: str = "count", errors_only: bool = False) -> dict:
+        """``novelty`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The report is
+        exactly the one-document report, whatever the chunk size."""
+        from .novelty import check_order
+        check_order(order)
+        acc = self._novelty_accumulator(baseline)
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(top, order, errors_only)
+
+    def novelty_resident(self, resident, baseline, top: Optional[int] = 20, order: str = "count",
+                         errors_only: bool = False) -> dict:
+        """``novelty`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        from .novelty import check_order
+        check_order(order)
+        acc = self._novelty_accumulator(baseline)
+        acc.add_resident(resident)
+        return acc.report(top, order, errors_only)
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

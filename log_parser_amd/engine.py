@@ -845,6 +845,22 @@ class Engine:
         from .timeline import timeline_document
         return timeline_document(self, text, n, data, bucket_seconds, max_buckets)
 
+    # ------------------------------------------------------------------ novelty report
+    def novelty_bytes(self, data: bytes, baseline, top: Optional[int] = 20, order: str = "count",
+                      errors_only: bool = False) -> dict:
+        """Which lines of one document have a template that ``baseline`` (a ``novelty.Baseline`` on
+        this engine's device) never saw, grouped by template? (novelty.py; ``golden.novelty`` is the
+        specification.) Nothing is scored and the frequency window is not touched."""
+        data = bytes(data)
+        text, n = self.stage_text(data)
+        return self.novelty_document(text, n, data, baseline, top=top, order=order, errors_only=errors_only)
+
+    def novelty_document(self, text, n: int, data: bytes, baseline, top: Optional[int] = 20, order: str = "count",
+                         errors_only: bool = False) -> dict:
+        """``novelty_bytes`` of a staged document: ``text`` = ``stage_text(data)``'s buffer."""
+        from .novelty import novelty_document
+        return novelty_document(self, text, n, data, baseline, top, order, errors_only)
+
     # documents larger than this are line-indexed on the GPU (k_nl_count/k_nl_write); smaller
     # batches are split on the host while they are being packed (memchr, no extra pass)
     GPU_SPLIT_BYTES = 32 << 20

@@ -74,6 +74,19 @@ def coverage(a: torch.Tensor, b: torch.Tensor, L: int) -> Optional[torch.Tensor]
     return (diff[:L].cumsum(0) > 0).to(torch.uint8)
 
 
+def record_examples(examples: Dict[int, Tuple[int, bytes]], sig: torch.Tensor, ordinal: torch.Tensor,
+                    win: torch.Tensor, raws: List[bytes]) -> None:
+    """The examples of a fold's winners (``GapTable.fold``; novelty.py keeps its examples the same
+    way): ``examples[signature] = (ordinal, raw line)`` for every pair ``win[i]`` with the raw line
+    ``raws[i]``, unless the group already has an example with a smaller ordinal. One read of the
+    winners' signatures and ordinals; one winner per NEW template in steady state."""
+    sigs, ords = torch.stack([sig[win], ordinal[win]]).cpu().tolist()
+    for s, o, raw in zip(sigs, ords, raws):
+        cur = examples.get(s)
+        if cur is None or o < cur[0]:
+            examples[s] = (o, raw)
+
+
 def gaps_document(eng: Engine, text, n: int, data: bytes, top: Optional[int] = 20, cover: str = "context") -> dict:
     """The report of a staged document in one piece (``Engine.gaps_document``): only the ``top``
     groups' numbers come back; the host renders template and example from its copy of the text."""
@@ -151,13 +164,7 @@ class GapAccumulator:
             return
         mine = win[win < n]
         if mine.numel():
-            raws = fetch(mine)
-            sigs, ords = torch.stack([sig[mine], ordinal[mine]]).cpu().tolist()
-            ex = self._examples
-            for s, o, raw in zip(sigs, ords, raws):         # (inlined _record: one winner per NEW template)
-                cur = ex.get(s)
-                if cur is None or o < cur[0]:
-                    ex[s] = (o, raw)
+            record_examples(self._examples, sig, ordinal, mine, fetch(mine))
         if held:
             for w in win[win >= n].tolist():
                 g, s, raw = held[w - n]

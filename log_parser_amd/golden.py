@@ -423,6 +423,78 @@ def gaps_corpus(docs, pattern_sets: List[PatternSet], params: ScoringParams, top
 
 
 # ---------------------------------------------------------------------------------------------
+# Novelty report (an extra, as the gap report): what does a log say that a baseline of healthy
+# logs never said? A line is *novel* when its template signature is not among the signatures of
+# the baseline's lines. These functions are the specification of ``log_parser_amd/novelty.py`` and
+# of the kernel that signs, probes and compacts in one pass (csrc/kernels/novelty.hip).
+#
+# Known limits are the signatures': two templates may share a 64-bit signature, and only the first
+# ``SIG_MAX_BYTES`` bytes of a line count.
+
+def _as_text(logs) -> str:
+    if isinstance(logs, (bytes, bytearray, memoryview)):
+        return bytes(logs).decode("utf-8", errors="surrogateescape")
+    return logs
+
+
+def baseline_signatures(docs):
+    """(set of signatures, lines, documents) of the baseline documents (str or bytes): every line
+    of every document (``split_lines``) contributes ``line_signature``; an empty line signs as the
+    empty template."""
+    sigs, n_lines, n_docs = set(), 0, 0
+    for d in docs:
+        n_docs += 1
+        for line in split_lines(_as_text(d)):
+            n_lines += 1
+            sigs.add(line_signature(line.encode("utf-8", errors="surrogateescape")))
+    return sigs, n_lines, n_docs
+
+
+def novelty(logs, baseline_docs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optional[int] = 20,
+            order: str = "count", errors_only: bool = False) -> dict:
+    """The novelty report of ``logs`` against the baseline documents: the lines whose signature
+    the baseline does not hold, grouped by signature. Per group: its lines (``count``), those that
+    are ``gap_candidate`` (``errorLines``), those an event of ``analyze`` lies on (``eventLines``:
+    the event's own line, not its context window) and its first line. ``order="count"``: most
+    frequent first (ties: first line); ``"first"``: by first line -- the first new thing that
+    happened. ``errors_only`` lists only the groups with error lines; the totals do not change."""
+    if order not in ("count", "first"):
+        raise ValueError("order must be 'count' or 'first'")
+    base, b_lines, b_docs = baseline_signatures(baseline_docs)
+    logs = _as_text(logs)
+    res = analyze(logs, pattern_sets, params, FrequencyTracker(params))
+    lines = split_lines(logs)
+    on_event = {e["lineNumber"] - 1 for e in res["events"]}
+    groups: Dict[int, list] = {}                # signature -> [count, error lines, event lines, first line, raw]
+    n_cand = n_novel = n_novel_cand = 0
+    for i, line in enumerate(lines):
+        cand = bool(gap_candidate(line))
+        n_cand += cand
+        raw = line.encode("utf-8", errors="surrogateescape")
+        sig = line_signature(raw)
+        if sig in base:
+            continue
+        n_novel += 1
+        n_novel_cand += cand
+        g = groups.setdefault(sig, [0, 0, 0, i, raw])
+        g[0] += 1
+        g[1] += cand
+        g[2] += i in on_event
+    listed = [kv for kv in groups.items() if kv[1][1] or not errors_only]
+    listed.sort(key=(lambda kv: (-kv[1][0], kv[1][3])) if order == "count" else (lambda kv: kv[1][3]))
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    return {"totalLines": len(lines), "events": len(res["events"]), "errorLines": n_cand,
+            "novelLines": n_novel, "novelErrorLines": n_novel_cand,
+            "templates": len(groups), "errorTemplates": sum(1 for g in groups.values() if g[1]),
+            "baseline": {"documents": b_docs, "lines": b_lines, "templates": len(base)},
+            "top": [{"count": c, "errorLines": ce, "eventLines": cv, "firstLine": i + 1, "signature": "%016x" % sig,
+                     "template": line_template(raw).decode("utf-8", errors="replace"),
+                     "example": raw.decode("utf-8", errors="replace")}
+                    for sig, (c, ce, cv, i, raw) in listed]}
+
+
+# ---------------------------------------------------------------------------------------------
 # Log timeline (an extra: the reference reads no time a log line carries). When did the lines, the
 # error lines and the events of a log happen? These functions are the specification of
 # ``Engine.timeline_bytes`` and of the timestamp kernel (csrc/kernels/ts_core.h).

@@ -986,10 +986,12 @@ class GapTable:
             N.gap_reinsert(self._tab(), tuple(c.data_ptr() for c in rows), used, _s(self._key), self._cuda)
             self._used[0] = used
 
-    def fold(self, sig: torch.Tensor, ord: torch.Tensor, doc: int = 0) -> torch.Tensor:
+    def fold(self, sig: torch.Tensor, ord: torch.Tensor, doc: int = 0, winners: bool = True) -> torch.Tensor:
         """Fold the pairs (sig[i], ord[i]) of document ``doc`` (one document per call, numbers never
         decreasing) into the table. Returns the indices (int64, no particular order) of the pairs
-        that hold their group's smallest ordinal after this call."""
+        that hold their group's smallest ordinal after this call -- or, with ``winners=False``
+        (a caller that keeps no examples), nothing: k_gap_winners and the read of its count are
+        left out."""
         n = sig.numel()
         if ord.numel() != n:
             raise ValueError("GapTable.fold: sig and ord differ in length")
@@ -1011,10 +1013,90 @@ class GapTable:
         self._last_doc = doc
         tab, st = self._tab(), _s(self._key)
         N.gap_fold(tab, sig.data_ptr(), ord.data_ptr(), n, doc, st, self._cuda, self.tile)
+        if not winners:
+            return torch.empty(0, dtype=torch.int64, device=self.device)
         out = torch.empty(n, dtype=torch.int64, device=self.device)
         cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
         N.gap_winners(tab, sig.data_ptr(), ord.data_ptr(), n, out.data_ptr(), cnt.data_ptr(), st, self._cuda)
         return out[:int(cnt.item())]
+
+    def contains(self, sig: torch.Tensor) -> torch.Tensor:
+        """bool[n]: the table holds sig[i] (k_gap_contains or its host twin)."""
+        sig = sig.to(device=self.device, dtype=torch.int64).contiguous()
+        out = torch.empty(sig.numel(), dtype=torch.uint8, device=self.device)
+        if sig.numel():
+            N.gap_contains(self._tab(), sig.data_ptr(), sig.numel(), out.data_ptr(), _s(self._key), self._cuda)
+        return out.bool()
+
+    @classmethod
+    def from_signatures(cls, device, sig: torch.Tensor, cap: Optional[int] = None) -> "GapTable":
+        """A table that holds exactly the DISTINCT signatures ``sig`` (count 1 each, first ordinal
+        0), built with k_gap_reinsert. ``cap``: a capacity of its own (a power of two >= n; tests:
+        a full table, wrap-around probing) instead of the smallest that keeps the table at most
+        half full. ValueError on duplicates."""
+        sig = sig.to(device=torch.device(device), dtype=torch.int64).contiguous()
+        n = sig.numel()
+        if n and torch.unique(sig).numel() != n:
+            raise ValueError("GapTable.from_signatures: duplicate signatures")
+        if cap is None:
+            cap = 1 << 12
+            while 2 * n > cap:
+                cap *= 2
+        elif cap < n:
+            raise ValueError("GapTable.from_signatures: cap below the number of signatures")
+        tab = cls(device, cap=cap)
+        if n:
+            dev = tab.device
+            rows = (sig, torch.ones(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                    torch.ones(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+            N.gap_reinsert(tab._tab(), tuple(c.data_ptr() for c in rows), n, _s(tab._key), tab._cuda)
+            tab._used[0] = n
+            tab._bound = n
+            tab._last_doc = 0
+        return tab
+
+
+# ---------------------------------------------------------------------------------------------
+# novelty report (csrc/kernels/novelty.hip): the lines whose template a baseline table does not hold
+
+NV_MAX_LINES = 2048         # lines per block of k_novel_sig at most
+NV_CAND, NV_EVENT = 1, 2    # flag bits of a novel line: gap candidate, an event lies on it
+
+
+def novel_lines(text, line_start, line_len, table: GapTable, feat: Optional[torch.Tensor] = None,
+                ev_mask: Optional[torch.Tensor] = None, cap: Optional[int] = None, per_block: int = 0):
+    """Every line whose template signature ``table`` does not hold: (line int32[n], signature
+    int64[n], flag uint8[n], (candidates among all lines, novel lines, novel candidates)). Flag
+    bit0: the line is a gap candidate of ``feat`` (uint8[L] context features; None: no candidates),
+    bit1: ``ev_mask`` (uint8[L]; None: no events) is set. One pass over the text (k_novel_sig) with
+    the capacity protocol of ``gap_lines``; ``cap=None`` starts well below L -- a mostly healthy
+    log has few novel lines. ``per_block``: lines per block instead of the size the launch picks
+    (tests). GPU: the triples come in no particular order; CPU: in line order."""
+    dev = text.device
+    L = line_start.numel()
+    if table.device != dev:
+        raise ValueError("novel_lines: the table lives on %s, the text on %s" % (table.device, dev))
+    for name, m in (("feat", feat), ("ev_mask", ev_mask)):
+        if m is not None and (m.dtype != torch.uint8 or m.numel() < L or not m.is_contiguous() or m.device != dev):
+            raise ValueError("novel_lines: %s must be contiguous uint8[L] on the text's device" % name)
+    if per_block and not 0 < per_block <= NV_MAX_LINES:
+        raise ValueError("novel_lines: per_block must be 1..%d" % NV_MAX_LINES)
+    if L == 0:
+        return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.uint8, device=dev), (0, 0, 0))
+    cap = max(1024, L // 16) if cap is None else max(0, int(cap))
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_sig = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        out_flag = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(3, dtype=torch.int64, device=dev)
+        N.novel_sig(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, table._tab(),
+                    _p(feat), _p(ev_mask), out_line.data_ptr(), out_sig.data_ptr(), out_flag.data_ptr(), cap,
+                    cnt.data_ptr(), _s(text), text.is_cuda, per_block)
+        n_cand, n, n_ncand = cnt.tolist()
+        if n <= cap:
+            return out_line[:n], out_sig[:n], out_flag[:n], (n_cand, n, n_ncand)
+        cap = n
 
 
 # ---------------------------------------------------------------------------------------------

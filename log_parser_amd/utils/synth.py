@@ -353,3 +353,36 @@ def make_log(n_lines: int, triggers: List[dict], seed: int = 0, hit_rate: float 
             parts.append("\r\n" if rng.random() < crlf_rate else "\n")
         return "".join(parts)
     return sep.join(out) + sep
+
+
+def log_templates(n: int, seed: int = 0) -> List[str]:
+    """``n`` distinct line templates with ``%d`` / ``%x`` fields: a level, a component, a few
+    words that never hold a digit, one to four fields. About one in eight is an error line."""
+    rng = random.Random(seed)
+    out, seen = [], set()
+    while len(out) < n:
+        lvl = "ERROR" if rng.random() < 0.125 else rng.choice(("INFO", "DEBUG", "WARN", "TRACE"))
+        words = [rng.choice(WORDS) for _ in range(rng.randint(3, 9))]
+        for _ in range(rng.randint(1, 4)):
+            words.insert(rng.randrange(len(words) + 1), rng.choice(("%d", "id=%d", "%dms", "0x%x", "node-%d")))
+        t = "2025-09-19T12:%02d:%02d.%03dZ " + f"{lvl:5s} [{rng.choice(COMPONENTS)}] " + " ".join(words)
+        key = t.replace("0x%x", "%d").replace("%dms", "%d")     # (fields that sign alike: one digit token)
+        if key not in seen:
+            seen.add(key)
+            out.append(t)
+    return out
+
+
+def templated_log(n_lines: int, templates: List[str], seed: int = 0, crlf_rate: float = 0.0) -> str:
+    """A log of ``n_lines`` lines drawn from ``templates`` (``log_templates``) with a skewed
+    frequency (a few templates make most of the log, as real logs do) and random numbers in the
+    fields: the set of line templates of the log is known by construction. The first three fields
+    of a template are the stamp's minute, second and millisecond."""
+    rng = random.Random(seed)
+    weights = [1.0 / (k + 1) for k in range(len(templates))]
+    parts = []
+    for i, t in enumerate(rng.choices(templates, weights=weights, k=n_lines)):
+        nf = t.count("%") - 3
+        parts.append(t % ((i // 60) % 60, i % 60, i % 1000, *(rng.randrange(1, 1 << 20) for _ in range(nf))))
+        parts.append("\r\n" if rng.random() < crlf_rate else "\n")
+    return "".join(parts)
