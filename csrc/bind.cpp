@@ -1226,6 +1226,40 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("eff"), py::arg("feat"), py::arg("L"), py::arg("ev_line"), py::arg("ev_pat"), py::arg("E"),
         py::arg("sev_index"), py::arg("npat"), py::arg("S"), py::arg("t0"), py::arg("W"), py::arg("nb"),
         py::arg("hist"), py::arg("stream"), py::arg("dev"));
+  // ---- trace report (traces.hip): line classes and signature elements, one row per stack trace
+  m.def("trace_tile", &trace_tile);
+  m.def("trace_runs_tmp_bytes", &trace_runs_tmp_bytes, py::arg("L"));
+  m.def("trace_class", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t cls, uint64_t elem,
+                          uint64_t s, bool dev) {
+    if (dev) {
+      trace_class_dev(P<const uint8_t>(text), tbytes, P<const int64_t>(ls), P<const int32_t>(ll), L, P<uint8_t>(cls),
+                      P<uint64_t>(elem), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    trace_class_host(P<const uint8_t>(text), tbytes, P<const int64_t>(ls), P<const int32_t>(ll), L, P<uint8_t>(cls),
+                     P<uint64_t>(elem)); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("cls"), py::arg("elem"),
+        py::arg("stream"), py::arg("dev"));
+  // carry: TR_CARRY_WORDS ints (open, pow, val, frames, causes, lines, event, headless, start, first
+  // FRAME line, last CAUSE line, event on the previous line, there is a previous line)
+  m.def("trace_runs", [](uint64_t cls, uint64_t elem, uint64_t evm, int64_t L, std::vector<int64_t> carry, bool last,
+                         uint64_t out, int64_t cap, uint64_t cnt, uint64_t carry_out, uint64_t tmp, uint64_t s, bool dev) {
+    if ((int)carry.size() != TR_CARRY_WORDS) throw std::runtime_error("trace_runs: the carry has 13 words");
+    TraceRunArgs A;
+    A.cls = P<const uint8_t>(cls); A.elem = P<const uint64_t>(elem); A.evm = P<const uint8_t>(evm); A.L = L;
+    A.in = TrCarry{carry[0], (uint64_t)carry[1], (uint64_t)carry[2], carry[3], carry[4], carry[5], carry[6], carry[7],
+                   carry[8], carry[9], carry[10], carry[11], carry[12]};
+    A.last = last;
+    A.out = P<int64_t>(out); A.cap = cap; A.cnt = P<unsigned long long>(cnt); A.carry_out = P<int64_t>(carry_out);
+    if (dev) {
+      trace_runs_dev(A, P<void>(tmp), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    trace_runs_host(A); },
+        py::arg("cls"), py::arg("elem"), py::arg("evm"), py::arg("L"), py::arg("carry"), py::arg("last"), py::arg("out"),
+        py::arg("cap"), py::arg("cnt"), py::arg("carry_out"), py::arg("tmp"), py::arg("stream"), py::arg("dev"));
   m.def("scan_multi", [](uint64_t text, int64_t nbytes, uint64_t ls, uint64_t ll, int64_t nl, py::tuple pass,
                          uint64_t out, int64_t cap, uint64_t cnt, int grid, uint64_t s, bool dev) -> int64_t {
     const ScanPass S = scan_pass_from(pass);

@@ -479,3 +479,37 @@ struct TlHistArgs {
 void tl_hist_dev(const TlHistArgs& A, uint64_t stream);
 void tl_hist_host(const TlHistArgs& A);
 }  // namespace lp
+
+// ---- trace report (traces.hip): stack traces as runs of frame / cause lines, one row per trace
+#include "trace_core.h"
+namespace lp {
+// cls[i] = class of line i (TR_OTHER / TR_FRAME / TR_MORE / TR_CAUSE), elem[i] = what it contributes
+// to its trace's signature (0 for OTHER and MORE); text: 16-byte aligned on the device
+void trace_class_dev(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, uint8_t* cls,
+                     uint64_t* elem, uint64_t stream);
+void trace_class_host(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, uint8_t* cls,
+                      uint64_t* elem);
+struct TraceRunArgs {
+  const uint8_t* cls;        // [L]
+  const uint64_t* elem;      // [L]
+  const uint8_t* evm = nullptr;   // [L] 1 where an event lies on the line, or null
+  int64_t L;                 // 1 .. 2^31 - 1
+  TrCarry in;                // what the previous piece left (line numbers count from this piece's first line)
+  bool last;                 // no later piece follows: a run that reaches the last line ends there
+  // outputs: one row per trace that ends in this piece, the first `cap` of them, as TR_COLS columns
+  // of `cap` entries each (start line, signature, lines, frames, causes, flags, first FRAME line,
+  // last CAUSE line; line numbers count from this piece's first line and are negative for a run
+  // that came in); cnt[0] += the traces (all of them: above cap the caller re-runs);
+  // carry_out[TR_CARRY_WORDS]: what this piece leaves, counted from the next piece's first line
+  int64_t* out;
+  int64_t cap;
+  unsigned long long* cnt;   // [1], zeroed by the caller
+  int64_t* carry_out;
+};
+int trace_tile();            // lines per block of the three scan launches
+int64_t trace_runs_tmp_bytes(int64_t L);
+// GPU: the rows come in no particular order. tmp: trace_runs_tmp_bytes(L) bytes, 8-byte aligned
+void trace_runs_dev(const TraceRunArgs& A, void* tmp, uint64_t stream);
+// appends in line order
+void trace_runs_host(const TraceRunArgs& A);
+}  // namespace lp

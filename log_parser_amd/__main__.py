@@ -21,6 +21,11 @@
             [--order count|first] [--errors-only]
                                                the lines of a log whose template a baseline of
                                                healthy logs never showed, grouped by template (JSON)
+  traces    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--top N]
+            [--order count|first] [--unexplained-only]
+                                               the stack traces of a log grouped by their frames and
+                                               causes: how often, where first, the root cause, and
+                                               whether an event lies on them (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -140,6 +145,17 @@ def cmd_novel(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_traces(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    kw = {"top": args.top, "order": args.order, "unexplained_only": args.unexplained_only}
+    if args.stream:
+        rep = lp.traces_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+    else:
+        rep = lp.traces_file(args.file, **kw)
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -186,11 +202,20 @@ def main(argv: Optional[List[str]] = None) -> int:
     n.add_argument("--order", choices=("count", "first"), default="count",
                    help="most frequent first (default), or in order of first appearance")
     n.add_argument("--errors-only", action="store_true", help="list only the groups with error lines")
+    r = sub.add_parser("traces", help="stack traces of a log file grouped by their frames and causes")
+    r.add_argument("file")
+    _library_options(r)
+    r.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    r.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    r.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
+    r.add_argument("--order", choices=("count", "first"), default="count",
+                   help="most frequent first (default), or in order of first appearance")
+    r.add_argument("--unexplained-only", action="store_true", help="list only the groups no event lies on")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
-            "timeline": cmd_timeline, "novel": cmd_novel}[args.cmd](args, cfg)
+            "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

@@ -39,6 +39,7 @@ SOURCES = [
     ("kernels/gap_table.hip", "hip"),
     ("kernels/novelty.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
+    ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),
     ("io/json_in.cpp", "cpp"),

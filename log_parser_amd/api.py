@@ -25,6 +25,9 @@ to embedders, with what an in-process user needs beyond one call at a time:
 * ``baseline`` / ``novelty`` / ``novelty_file``: the lines of a log whose template a baseline of
   healthy logs never showed, grouped by template; ``novelty_stream`` / ``novelty_resident`` for
   one log too large for one piece;
+* ``traces`` / ``traces_file``: the stack traces of a log grouped by their frames and causes --
+  how often, where first, the root cause, whether an event explains them; ``traces_stream`` /
+  ``traces_resident`` for one log too large for one piece;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -306,6 +309,55 @@ class LogParser:
         acc = self._novelty_accumulator(baseline)
         acc.add_resident(resident)
         return acc.report(top, order, errors_only)
+
+    # ---- trace report -------------------------------------------------------------------------
+    def traces(self, logs, top: Optional[int] = 20, order: str = "count", unexplained_only: bool = False) -> dict:
+        """Which stack traces does one document (str or bytes) hold? Runs of ``at`` frames,
+        ``Caused by:`` / ``Suppressed:`` lines and ``... n more`` (the JVM's and Node's shape),
+        grouped by their frames and cause classes -- line numbers do not matter: per group how many
+        traces, how many of them an event lies on, where it first appears, and of its first trace
+        the head, the exception named there, the top frame and the root cause. ``order="count"``:
+        most frequent first; ``"first"``: in order of first appearance. ``unexplained_only`` lists
+        only the groups no event lies on (the totals do not change); ``top=None``: every group.
+        ``Engine.traces_bytes``; ``golden.traces`` is the specification; the frequency window is
+        not touched."""
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("traces"):
+            return self.engine.traces_bytes(logs, top=top, order=order, unexplained_only=unexplained_only)
+
+    def traces_file(self, path: str, top: Optional[int] = 20, order: str = "count",
+                    unexplained_only: bool = False) -> dict:
+        """``traces`` of a log file, read as ONE document whatever its size."""
+        with open(path, "rb") as f:
+            return self.traces(f.read(), top=top, order=order, unexplained_only=unexplained_only)
+
+    def _trace_accumulator(self):
+        from .traces import TraceAccumulator
+        with self._engine_guard("traces"):
+            return TraceAccumulator(self.engine, guard=lambda: self._engine_guard("traces"))
+
+    def traces_stream(self, src_or_path, chunk_bytes: Optional[int] = None, top: Optional[int] = 20,
+                      order: str = "count", unexplained_only: bool = False) -> dict:
+        """``traces`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). A trace may straddle
+        any number of chunks; the report is exactly the one-document report, whatever the chunk
+        size."""
+        from .novelty import check_order
+        check_order(order)
+        acc = self._trace_accumulator()
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(top, order, unexplained_only)
+
+    def traces_resident(self, resident, top: Optional[int] = 20, order: str = "count",
+                        unexplained_only: bool = False) -> dict:
+        """``traces`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        from .novelty import check_order
+        check_order(order)
+        acc = self._trace_accumulator()
+        acc.add_resident(resident)
+        return acc.report(top, order, unexplained_only)
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

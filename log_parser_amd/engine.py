@@ -861,6 +861,22 @@ class Engine:
         from .novelty import novelty_document
         return novelty_document(self, text, n, data, baseline, top, order, errors_only)
 
+    # ------------------------------------------------------------------ trace report
+    def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
+                     unexplained_only: bool = False) -> dict:
+        """Which stack traces does one document hold, grouped by their frames and causes: how often,
+        where first, with which root cause, and does an event lie on them? (traces.py;
+        ``golden.traces`` is the specification.) Nothing is scored, the frequency window is not
+        touched."""
+        text, n = self.stage_text(data)
+        return self.traces_document(text, n, data, top=top, order=order, unexplained_only=unexplained_only)
+
+    def traces_document(self, text, n: int, data: bytes, top: Optional[int] = 20, order: str = "count",
+                        unexplained_only: bool = False) -> dict:
+        """``traces_bytes`` of a staged document: ``text`` = ``stage_text(data)``'s buffer."""
+        from .traces import traces_document
+        return traces_document(self, text, n, data, top, order, unexplained_only)
+
     # documents larger than this are line-indexed on the GPU (k_nl_count/k_nl_write); smaller
     # batches are split on the host while they are being packed (memchr, no extra pass)
     GPU_SPLIT_BYTES = 32 << 20

@@ -612,3 +612,141 @@ def timeline(logs, pattern_sets: List[PatternSet], params: ScoringParams, bucket
         out["lastEvent"] = ref
     out["buckets"] = [{"start": iso_ms(t), **buckets[t]} for t in sorted(buckets)]
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Trace report (an extra, as the gap report): which stack traces does a log hold, how often, where
+# first, with which root cause, and does any pattern explain them? These functions are the
+# specification of ``log_parser_amd/traces.py`` and of the line classifier and the run scan
+# (csrc/kernels/trace_core.h, traces.hip).
+#
+# The shape is the JVM's and Node's: the exception first, then ``at`` frames, ``Caused by:`` /
+# ``Suppressed:`` lines and ``... n more``. Not covered: Python tracebacks (the exception comes
+# last there), Go panics, and exception messages of several lines before the first frame (only
+# the line just before the run is the head). The bounds of the regexes let the device classify a
+# line from a bounded prefix.
+
+TR_OTHER, TR_FRAME, TR_MORE, TR_CAUSE = 0, 1, 2, 3
+TR_TOKEN_MAX = 256
+_TR_FRAME = re.compile(rb"^[ \t]{1,64}at[ \t]")
+_TR_MORE = re.compile(rb"^[ \t]{1,64}\.\.\.")
+_TR_CAUSE = re.compile(rb"^[ \t]{0,64}(?:Caused by:|Suppressed:)[ \t]{0,8}([^: \t]{0,256})")
+_TR_EXC = re.compile(rb"(?:[A-Za-z_$][\w$]*\.)*[A-Za-z_$][\w$]*(?:Exception|Error|Throwable)\b")
+_TR_M = 0x9E3779B97F4A7C15
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def fmix64(h: int) -> int:
+    """The finaliser of MurmurHash3 (``gt_hash`` of csrc/kernels/gap_table.h)."""
+    h &= _M64
+    h ^= h >> 33
+    h = (h * 0xff51afd7ed558ccd) & _M64
+    h ^= h >> 33
+    h = (h * 0xc4ceb9fe1a85ec53) & _M64
+    return h ^ (h >> 33)
+
+
+def fnv1a64(data: bytes) -> int:
+    h = _FNV_OFFSET
+    for c in data:
+        h = ((h ^ c) * _FNV_PRIME) & _M64
+    return h
+
+
+def trace_class(line: bytes):
+    """(class, cause token or None) of a line: the first of FRAME, MORE, CAUSE that matches, else OTHER."""
+    if _TR_FRAME.match(line):
+        return TR_FRAME, None
+    if _TR_MORE.match(line):
+        return TR_MORE, None
+    m = _TR_CAUSE.match(line)
+    if m:
+        return TR_CAUSE, m.group(1)
+    return TR_OTHER, None
+
+
+def trace_element(line: bytes) -> Optional[int]:
+    """What a run line contributes to its trace's signature: a frame its mixed template signature,
+    a cause the mixed complement of its token's hash, anything else nothing."""
+    cls, token = trace_class(line)
+    if cls == TR_FRAME:
+        return fmix64(line_signature(line))
+    if cls == TR_CAUSE:
+        return fmix64(~fnv1a64(token))
+    return None
+
+
+def trace_signature(run: Sequence[bytes]) -> int:
+    """``fmix64(V ^ k)`` with ``V = sum(e_i * M^(k - i))`` (mod 2^64) over the k contributing lines
+    of the run, in order. The head does not contribute; digits are normalised by the template, so
+    a trace keeps its signature across line-number changes."""
+    v = k = 0
+    for line in run:
+        e = trace_element(line)
+        if e is not None:
+            v = (v * _TR_M + e) & _M64
+            k += 1
+    return fmix64(v ^ k)
+
+
+def traces(logs, pattern_sets: List[PatternSet], params: ScoringParams, top: Optional[int] = 20,
+           order: str = "count", unexplained_only: bool = False) -> dict:
+    """The trace report of ``logs``. A run is a maximal sequence of consecutive non-OTHER lines; a
+    run with at least one FRAME is a trace, the line just before it its head (a run that starts
+    the document is headless). Traces are grouped by ``trace_signature``; per group its traces
+    (``count``), those with an event of ``analyze`` on the head or a run line (``eventTraces``),
+    where it first appears, and the shape of its first trace. ``order="count"``: most frequent
+    first (ties: first line); ``"first"``: by first line. ``unexplained_only`` lists only the
+    groups without an event; the totals do not change."""
+    if order not in ("count", "first"):
+        raise ValueError("order must be 'count' or 'first'")
+    logs = _as_text(logs)
+    res = analyze(logs, pattern_sets, params, FrequencyTracker(params))
+    lines = [x.encode("utf-8", errors="surrogateescape") for x in split_lines(logs)]
+    on_event = {e["lineNumber"] - 1 for e in res["events"]}
+    cls = [trace_class(x)[0] for x in lines]
+    groups: Dict[int, dict] = {}
+    n_traces = n_trace_lines = n_frames = n_unexplained = 0
+    i, n = 0, len(lines)
+    while i < n:
+        if cls[i] == TR_OTHER:
+            i += 1
+            continue
+        a = i
+        while i < n and cls[i] != TR_OTHER:
+            i += 1
+        run = range(a, i)
+        frames = [x for x in run if cls[x] == TR_FRAME]
+        if not frames:
+            continue
+        causes = [x for x in run if cls[x] == TR_CAUSE]
+        head = lines[a - 1] if a else None
+        event = any(x in on_event for x in range(a - 1 if a else a, i))
+        n_traces += 1
+        n_trace_lines += len(run) + (a > 0)
+        n_frames += len(frames)
+        n_unexplained += not event
+        g = groups.get(trace_signature(lines[a:i]))
+        if g is None:
+            exc = _TR_EXC.search(head) if head is not None else None
+            g = groups[trace_signature(lines[a:i])] = {
+                "count": 0, "eventTraces": 0, "firstLine": a if a else 1,
+                "lines": len(run) + (a > 0), "frames": len(frames), "causes": len(causes),
+                "head": head.decode("utf-8", errors="replace") if head is not None else None,
+                "exception": exc.group().decode("utf-8", errors="replace") if exc else None,
+                "topFrame": lines[frames[0]].strip(b" \t").decode("utf-8", errors="replace"),
+                "rootCause": lines[causes[-1]].strip(b" \t").decode("utf-8", errors="replace") if causes else None}
+        g["count"] += 1
+        g["eventTraces"] += event
+    listed = [kv for kv in groups.items() if not (unexplained_only and kv[1]["eventTraces"])]
+    listed.sort(key=(lambda kv: (-kv[1]["count"], kv[1]["firstLine"])) if order == "count"
+                else (lambda kv: kv[1]["firstLine"]))
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    return {"totalLines": n, "events": len(res["events"]), "traces": n_traces, "traceLines": n_trace_lines,
+            "frameLines": n_frames, "groups": len(groups), "unexplainedTraces": n_unexplained,
+            "unexplainedGroups": sum(1 for g in groups.values() if not g["eventTraces"]),
+            "top": [{"count": g["count"], "eventTraces": g["eventTraces"], "firstLine": g["firstLine"],
+                     "signature": "%016x" % sig, "lines": g["lines"], "frames": g["frames"], "causes": g["causes"],
+                     "head": g["head"], "exception": g["exception"], "topFrame": g["topFrame"],
+                     "rootCause": g["rootCause"]} for sig, g in listed]}

@@ -1170,3 +1170,94 @@ def timeline_hist(eff: torch.Tensor, feat: torch.Tensor, ev_line: torch.Tensor, 
         N.tl_hist(eff.data_ptr(), feat.data_ptr(), L, ev_line.data_ptr(), ev_pat.data_ptr(), E, sev_index.data_ptr(),
                   sev_index.numel(), S, int(t0), int(W), int(nb), hist.data_ptr(), _s(eff), eff.is_cuda)
     return hist
+
+
+# ---------------------------------------------------------------------------------------------
+# trace report (csrc/kernels/traces.hip): stack traces as runs of frame / cause lines
+
+TR_OTHER, TR_FRAME, TR_MORE, TR_CAUSE = 0, 1, 2, 3      # line classes (csrc/kernels/trace_core.h)
+TR_TILE = 1024              # lines per block of k_tr_tiles / k_tr_emit
+TR_COLS = 8                 # columns of a trace row:
+TR_START, TR_SIG, TR_LINES, TR_FRAMES, TR_CAUSES, TR_FLAGS, TR_FF, TR_LC = range(8)
+TR_ROW_EVENT, TR_ROW_HEADLESS = 1, 2                    # its flag bits
+TR_NO_CAUSE = -(1 << 63)    # last CAUSE line of a trace without one
+TR_CARRY_WORDS = 13
+# the words of a carry: an open run (pow and val as int64 bit patterns; line numbers count from
+# the next piece's first line), an event on the previous line, there is a previous line
+(TRC_OPEN, TRC_POW, TRC_VAL, TRC_FRAMES, TRC_CAUSES, TRC_LINES, TRC_EVENT, TRC_HEADLESS, TRC_START, TRC_FF, TRC_LC,
+ TRC_PREV_EVENT, TRC_HAS_PREV) = range(13)
+TR_CARRY_START = (0, 1, 0, 0, 0, 0, 0, 0, 0, (1 << 63) - 1, -(1 << 63), 0, 0)     # the document begins here
+
+
+def trace_classes(text, line_start, line_len) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(class uint8[L], element int64[L]) of every line: ``golden.trace_class`` and the bit pattern
+    of ``golden.trace_element`` (0 where a line contributes nothing). k_tr_class or its host twin;
+    the template signature is computed on FRAME lines only."""
+    L = line_start.numel()
+    dev = text.device
+    if line_start.dtype != torch.int64 or not line_start.is_contiguous() or line_start.device != dev:
+        raise ValueError("trace_classes: line_start must be contiguous int64[L] on the text's device")
+    if line_len.dtype != torch.int32 or line_len.numel() != L or not line_len.is_contiguous() or line_len.device != dev:
+        raise ValueError("trace_classes: line_len must be contiguous int32[L] on the text's device")
+    if text.dtype != torch.uint8 or not text.is_contiguous():
+        raise ValueError("trace_classes: text must be contiguous uint8")
+    cls = torch.empty(L, dtype=torch.uint8, device=dev)
+    elem = torch.empty(L, dtype=torch.int64, device=dev)
+    if L:
+        N.trace_class(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, cls.data_ptr(),
+                      elem.data_ptr(), _s(text), text.is_cuda)
+    return cls, elem
+
+
+def trace_runs(text, line_start, line_len, ev_mask: Optional[torch.Tensor] = None, carry=TR_CARRY_START,
+               last: bool = True, cap: Optional[int] = None):
+    """The stack traces that end in the lines (line_start, line_len) of ``text``, one piece of a
+    document: (columns int64[TR_COLS, n], (n,), carry_out). A run is a maximal sequence of
+    consecutive non-OTHER lines, a trace a run with a FRAME. Columns: start line, signature
+    (``golden.trace_signature``'s bit pattern), run lines, frames, causes, flags (bit0: an event
+    of ``ev_mask`` -- uint8[L]; None: no events -- lies on the head or a run line, bit1: headless),
+    first FRAME line, last CAUSE line (``TR_NO_CAUSE`` without one). Line numbers count from the
+    piece's first line; those of a run that came in with ``carry`` are negative. ``carry``: what
+    the previous piece's call returned (``TR_CARRY_START`` for the first piece); ``last``: no
+    piece follows, a run that reaches the last line ends there -- otherwise it goes out in
+    ``carry_out`` and no row is written for it yet. k_tr_class, then the segmented scan k_tr_tiles
+    / k_tr_prefix / k_tr_emit, or their host twins, with the capacity protocol of ``novel_lines``.
+    GPU: the rows come in no particular order; CPU: in line order."""
+    dev = text.device
+    L = line_start.numel()
+    carry = tuple(int(c) for c in carry)
+    if len(carry) != TR_CARRY_WORDS:
+        raise ValueError("trace_runs: the carry has %d words" % TR_CARRY_WORDS)
+    if ev_mask is not None and (ev_mask.dtype != torch.uint8 or ev_mask.numel() < L or not ev_mask.is_contiguous()
+                                or ev_mask.device != dev):
+        raise ValueError("trace_runs: ev_mask must be contiguous uint8[L] on the text's device")
+    if L == 0:
+        # no line: the carry passes through, or (last) the run that came in ends here
+        cols = torch.empty((TR_COLS, 0), dtype=torch.int64, device=dev)
+        if not last:
+            return cols, (0,), carry
+        out = (0, 1, 0, 0, 0, 0, 0, 0, 0) + TR_CARRY_START[9:11] + (carry[TRC_PREV_EVENT], carry[TRC_HAS_PREV])
+        if carry[TRC_OPEN] and carry[TRC_FRAMES] > 0:
+            cols = torch.tensor(_carry_row(carry), dtype=torch.int64, device=dev).reshape(TR_COLS, 1)
+        return cols, (int(cols.shape[1]),), out
+    cls, elem = trace_classes(text, line_start, line_len)
+    cap = max(64, L // 64) if cap is None else max(1, int(cap))
+    tmp = torch.empty(N.trace_runs_tmp_bytes(L) // 8, dtype=torch.int64, device=dev) if text.is_cuda else None
+    while True:
+        out = torch.empty((TR_COLS, cap), dtype=torch.int64, device=dev)
+        state = torch.zeros(1 + TR_CARRY_WORDS, dtype=torch.int64, device=dev)      # the count, then the carry out
+        N.trace_runs(cls.data_ptr(), elem.data_ptr(), _p(ev_mask), L, carry, bool(last), out.data_ptr(), cap,
+                     state.data_ptr(), state.data_ptr() + 8, _p(tmp), _s(text), text.is_cuda)
+        n, *carry_out = state.tolist()
+        if n <= cap:
+            return out[:, :n], (n,), tuple(carry_out)
+        cap = n
+
+
+def _carry_row(carry) -> list:
+    """The trace row of an open run that ends where it stands (csrc/kernels/trace_core.h tr_row)."""
+    from ..golden import fmix64
+    sig = fmix64((carry[TRC_VAL] ^ (carry[TRC_FRAMES] + carry[TRC_CAUSES])) & ((1 << 64) - 1))
+    flags = (TR_ROW_EVENT if carry[TRC_EVENT] else 0) | (TR_ROW_HEADLESS if carry[TRC_HEADLESS] else 0)
+    return [carry[TRC_START], sig - (1 << 64) if sig >> 63 else sig, carry[TRC_LINES], carry[TRC_FRAMES],
+            carry[TRC_CAUSES], flags, carry[TRC_FF], carry[TRC_LC]]

@@ -386,3 +386,46 @@ def templated_log(n_lines: int, templates: List[str], seed: int = 0, crlf_rate: 
         parts.append(t % ((i // 60) % 60, i % 60, i % 1000, *(rng.randrange(1, 1 << 20) for _ in range(nf))))
         parts.append("\r\n" if rng.random() < crlf_rate else "\n")
     return "".join(parts)
+
+
+def trace_sites(n: int, seed: int = 0) -> List[Tuple[str, List[str]]]:
+    """``n`` places that throw: (head template, run templates) with ``%d`` fields -- 2..12 ``at``
+    frames, for most sites a chain of one to three ``Caused by:`` (with frames and ``... n more``),
+    for some a ``Suppressed:`` entry. Distinct sites differ in their frames."""
+    rng = random.Random(seed)
+    excs = ("java.lang.IllegalStateException", "java.lang.OutOfMemoryError", "java.io.IOException",
+            "java.util.concurrent.TimeoutException", "com.acme.db.DeadlockError", "java.lang.NullPointerException")
+    out = []
+    for k in range(n):
+        pkg = "com.acme.%s" % rng.choice(WORDS)
+        run = ["\tat %s.S%d.call%d(S%d.java:%%d)" % (pkg, k, j, k) for j in range(rng.randint(2, 12))]
+        for c in range(rng.choice((0, 1, 1, 2, 3))):
+            run.append("Caused by: %s: %s %%d" % (rng.choice(excs), rng.choice(WORDS)))
+            run += ["\tat %s.C%d.step%d(C%d.java:%%d)" % (pkg, k, j, c) for j in range(rng.randint(1, 4))]
+            run.append("\t... %d more")
+        if k % 5 == 4:
+            run += ["\tSuppressed: %s.CloseFailed: %%d" % pkg, "\t\tat %s.Closer.close(Closer.java:%%d)" % pkg]
+        out.append(("2025-09-19T12:%02d:%02d.%03dZ ERROR [w-%d] " + "%s: %s failed" % (rng.choice(excs), pkg), run))
+    return out
+
+
+def traced_log(n_lines: int, templates: List[str], sites: List[Tuple[str, List[str]]], seed: int = 0,
+               trace_share: float = 0.1, crlf_rate: float = 0.0) -> str:
+    """About ``n_lines`` lines: ``templated_log`` lines with traces of ``sites`` (``trace_sites``)
+    planted among them until about ``trace_share`` of the lines belong to a trace."""
+    rng = random.Random(seed)
+    plain = templated_log(n_lines, templates, seed=seed, crlf_rate=crlf_rate).splitlines(keepends=True)
+    mean = sum(len(run) + 1 for _, run in sites) / max(len(sites), 1)
+    n_traces = int(n_lines * trace_share / mean)
+    keep = max(1, n_lines - int(n_traces * mean))
+    at = sorted(rng.randrange(keep) for _ in range(n_traces))
+    out, a = [], 0
+    for i, pos in enumerate(at):
+        out += plain[a:pos]
+        a = pos
+        head, run = sites[rng.randrange(len(sites))]
+        eol = "\r\n" if rng.random() < crlf_rate else "\n"
+        out.append(head % ((i // 60) % 60, i % 60, i % 1000, rng.randrange(64)) + eol)
+        out += [(x % rng.randrange(1, 2000) if "%d" in x else x) + eol for x in run]
+    out += plain[a:keep]
+    return "".join(out)
