@@ -1748,6 +1748,15 @@ PYBIND11_MODULE(_lpnative, m) {
     if (dev) blk_index_dev(P<const int64_t>(ls), L, nblocks, P<int32_t>(blk), s);
     else blk_index_host(P<const int64_t>(ls), L, nblocks, P<int32_t>(blk));
   });
+  // TEST-ONLY entry point (tests/test_prefilter_exact.py), no product code calls it: host-side
+  // locate_line (lp_core.h) for n byte positions, with the coarse block index (blk != 0) or without.
+  // The CPU prefilter never passes a block index, so this is how CPU tests reach that branch. Like
+  // its neighbours it trusts its pointers: blk must hold (last position >> 12) + 2 entries.
+  m.def("locate_lines_host", [](uint64_t ls, int64_t L, uint64_t blk, uint64_t pos, int64_t n, uint64_t out) {
+    const int64_t* p = P<const int64_t>(pos);
+    int64_t* o = P<int64_t>(out);
+    for (int64_t i = 0; i < n; ++i) o[i] = locate_line(P<const int64_t>(ls), L, P<const int32_t>(blk), p[i]);
+  });
 
   m.def("seq_chain", [](uint64_t slot_seq, uint64_t off, uint64_t reg, uint64_t hoff, uint64_t hline, int32_t lo,
                         int32_t hi, int n, uint64_t out, uint64_t s, bool dev) {

@@ -61,12 +61,19 @@ class HostPool {
     for (int k = 0; k < std::min(helpers, sleeping); ++k) cv_.notify_one();
     work();
     // wait until every item is done AND every worker that joined has left work(): the region's
-    // state is only rewritten while no worker can read it
-    while (done_.load(std::memory_order_acquire) < n_ || active_.load(std::memory_order_acquire) > 0)
-      std::this_thread::yield();
-    std::lock_guard<std::mutex> g(m_);   // late joiners see want_ = 0 and skip this region
-    fn_ = nullptr;
-    want_ = 0;
+    // state is only rewritten while no worker can read it. Workers join (active_) under m_, so the
+    // region is closed under m_ with active_ read again: a worker that joined between the wait and
+    // the lock would otherwise still be inside work() when the next region resets next_ / n_, and
+    // run one of its items a second time, beside the thread that owns it.
+    for (;;) {
+      while (done_.load(std::memory_order_acquire) < n_ || active_.load(std::memory_order_acquire) > 0)
+        std::this_thread::yield();
+      std::lock_guard<std::mutex> g(m_);   // late joiners see want_ = 0 and skip this region
+      if (active_.load(std::memory_order_acquire) > 0) continue;
+      fn_ = nullptr;
+      want_ = 0;
+      break;
+    }
   }
 
  private:

@@ -750,3 +750,32 @@ def traces(logs, pattern_sets: List[PatternSet], params: ScoringParams, top: Opt
                      "signature": "%016x" % sig, "lines": g["lines"], "frames": g["frames"], "causes": g["causes"],
                      "head": g["head"], "exception": g["exception"], "topFrame": g["topFrame"],
                      "rootCause": g["rootCause"]} for sig, g in listed]}
+
+
+# ------------------------------------------------------------------ literal prefilter oracle
+def literal_candidates(lib, data: bytes, line_start):
+    """Exact candidates of the literal prefilter (ops.kernels.prefilter) as a multiset of keys
+    ``regex << 32 | line``: for every literal of ``lib.literals``, every (overlapping) occurrence in
+    the ASCII-lower-cased text and every regex the literal belongs to, one key, where ``line`` is
+    the index of the last ``line_start <= position``. Unordered: a ``collections.Counter``."""
+    import collections
+
+    import numpy as np
+    low = bytes(data).lower()                       # ASCII only: bytes >= 0x80 stay as they are
+    ls = np.asarray(line_start.cpu() if hasattr(line_start, "cpu") else line_start, dtype=np.int64)
+    pf = lib.pf
+    out: collections.Counter = collections.Counter()
+    for i, lit in enumerate(lib.literals):
+        pos = []
+        p = low.find(lit)
+        while p >= 0:
+            pos.append(p)
+            p = low.find(lit, p + 1)
+        if not pos:
+            continue
+        lines = np.maximum(np.searchsorted(ls, np.array(pos, np.int64), side="right") - 1, 0)
+        per_line = collections.Counter(lines.tolist())
+        for r in pf["lit_reg"][int(pf["lit_reg_off"][i]):int(pf["lit_reg_off"][i + 1])]:
+            for line, c in per_line.items():
+                out[(int(r) << 32) | int(line)] += c
+    return out

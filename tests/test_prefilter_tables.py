@@ -1,7 +1,9 @@
 """Prefilter tables (models/compiled.py _build_prefilter): with stride-S sampling (S = 2 or 4) every
 literal indexes S adjacent 4-byte windows, so every occurrence of a literal has an indexed window that
 starts at a text position divisible by S -- the positions k_prefilter<16, S> tests. Checked here on the
-tables themselves (the device kernel is covered by the GPU tests against the golden model)."""
+tables themselves and on the host twin; the GPU test here compares the device with the host twin and
+the golden model on synthetic logs only. The device kernels' exact-search oracle, variant by variant
+and edge by edge, is tests/test_prefilter_exact.py."""
 import random
 
 import numpy as np
