@@ -779,3 +779,124 @@ def literal_candidates(lib, data: bytes, line_start):
             for line, c in per_line.items():
                 out[(int(r) << 32) | int(line)] += c
     return out
+
+
+# ------------------------------------------------------------------ score oracle on hand-built tables
+# The seven factors over HIT SETS instead of text: what proximity_factor, temporal_factor,
+# context_factor, chronological_factor and FrequencyTracker.penalty above compute once "the regex
+# finds line j" is replaced by "j is in the regex's set of lines" and the context regexes by a
+# line's feature bits. Linear scans only; this is the specification of csrc/kernels/lp_core.h's
+# score (host loop, k_score, request tail) on tables a test lays out by hand.
+
+def exp_correctly_rounded(num: float, den: float) -> float:
+    """The double nearest to exp(num / den), the quotient of the two doubles taken exactly (60
+    digits, never rounded to a double first). ``Decimal.exp`` is correctly rounded at context
+    precision; ``float()`` of a Decimal is the correctly rounded conversion."""
+    import decimal
+    with decimal.localcontext() as c:
+        c.prec = 60
+        return float((decimal.Decimal(num) / decimal.Decimal(den)).exp())
+
+
+def score_reference(tables: dict, params: ScoringParams, events, carry):
+    """Scores of ``events`` on hand-built tables, in plain Python.
+
+    ``tables``:
+      ``patterns``  list of dicts: ``conf``, ``sev`` (floats), ``context`` (``None`` = rules null,
+                    else ``(lines_before, lines_after)``), ``secondaries`` (list of ``(regex,
+                    window, weight)``, regex -1 = none, window already clamped to
+                    ``max_window`` as the compiled library does) and ``sequences`` (list of ``(bonus,
+                    [regex per event], [carry flag per event])``)
+      ``hits``      per regex, the ``set`` of batch-local lines it matches
+      ``feat``      per batch-local line, the context bits: 1 ERROR, 2 WARN, 4 stack frame, 8 exception
+      ``segments``  list of ``(lo, hi, own_lo, g0, n)``: a document (or shard with its halo) holds the
+                    batch-local lines ``[lo, hi)``; line ``lo`` is global line ``g0`` of an ``n``-line log;
+                    a sequence chain searches back to ``own_lo`` and an event it misses there counts
+                    as found exactly when its carry flag is set (the chain was completed by an
+                    earlier shard)
+    ``events``: list of ``(line, pattern, segment, rank, key)``; the frequency count before the event is
+    ``carry[key] + rank``, and ``key`` -1 is a pattern without an id.
+
+    Returns one dict per event: ``factors`` (confidence, severity, chronological, proximity,
+    temporal, context, penalty), ``score`` (their left-to-right product, ScoringService.java:102-109)
+    and ``prox_terms`` (the ``(weight, distance)`` of every secondary that counted). The proximity
+    factor uses ``exp_correctly_rounded``; everything else is the double arithmetic of the functions
+    above."""
+    hits = [set(h) for h in tables["hits"]]
+    feat = tables["feat"]
+    out = []
+    for x, p, s, rank, key in events:
+        pat = tables["patterns"][p]
+        lo, hi, own_lo, g0, n = tables["segments"][s]
+        chrono = chronological_factor(g0 + (x - lo), n, params)
+
+        prox, terms = 1.0, []
+        if pat["secondaries"]:
+            total = 0.0
+            for r, w, weight in pat["secondaries"]:
+                near = [abs(j - x) for j in range(max(lo, x - w), min(hi, x + w + 1))
+                        if j != x and r >= 0 and j in hits[r]]
+                if near:
+                    d = float(min(near))
+                    total += weight * exp_correctly_rounded(-d, params.decay_constant)
+                    terms.append((weight, d))
+            prox = 1.0 + total
+
+        temp = 1.0
+        if pat["sequences"]:
+            total = 0.0
+            for bonus, regs, flags in pat["sequences"]:
+                if not regs:
+                    continue
+                last = regs[-1]
+                if not any(last >= 0 and j in hits[last] for j in range(max(lo, x - 5), min(hi, x + 5 + 1))):
+                    continue
+                ok, cursor = True, x
+                for k in range(len(regs) - 2, -1, -1):
+                    found = -1
+                    for j in range(cursor - 1, own_lo - 1, -1):
+                        if regs[k] >= 0 and j in hits[regs[k]]:
+                            found = j
+                            break
+                    if found < 0:
+                        ok = bool(flags[k])
+                        break
+                    cursor = found
+                if ok:
+                    total += bonus
+            temp = 1.0 + total
+
+        window = [x]
+        if pat["context"] is not None:
+            before, after = pat["context"]
+            window = list(range(max(lo, x - max(0, before)), min(hi, x + 1 + max(0, after))))
+        sc, err, stack = 0.0, 0, 0
+        for j in window:
+            f = feat[j]
+            if f & 1:
+                err += 1
+                sc += 0.4
+            elif f & 2:
+                sc += 0.2
+            if f & 4:
+                stack += 1
+                sc += 0.1
+            if f & 8:
+                sc += 0.3
+        if stack > 0:
+            sc += min(stack * 0.1, 0.5)
+        if len(window) > 10 and (stack + err) > len(window) * 0.7:
+            sc *= 0.8
+        ctx = min(1.0 + sc, params.max_context_factor)
+
+        pen = 0.0
+        if key >= 0:
+            rate = (carry[key] + rank) / float(params.freq_window_hours)
+            if rate > params.freq_threshold:
+                pen = min(params.freq_max_penalty, (rate - params.freq_threshold) / params.freq_threshold)
+
+        conf, sev = pat["conf"], pat["sev"]
+        out.append({"factors": [conf, sev, chrono, prox, temp, ctx, pen],
+                    "score": conf * sev * chrono * prox * temp * ctx * (1.0 - pen),
+                    "prox_terms": terms})
+    return out

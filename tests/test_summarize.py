@@ -77,21 +77,44 @@ def test_topk_rows_merge_cpu():
     np.testing.assert_array_equal(got, fin[order])
 
 
-def test_rescore_matches_reference_order():
-    from log_parser_amd.engine import Engine
-    from log_parser_amd.golden import chronological_factor
+# every field off its default and different from every other one (tests/test_score_oracle.py)
+def _rescore_params():
     from log_parser_amd.utils.config import ScoringParams
-    p = ScoringParams()
-    sp = Engine.score_param_tuple(p)
-    rng = np.random.default_rng(7)
-    n, N = 4000, 12345
-    gl = np.sort(rng.integers(0, N, size=n)).astype(np.int64)
+    return [ScoringParams(),
+            ScoringParams(decay_constant=6.0, max_window=7, early_bonus_threshold=0.25, max_early_bonus=3.5,
+                          penalty_threshold=0.75, max_context_factor=1.75, freq_threshold=2.0, freq_max_penalty=0.5,
+                          freq_window_hours=3)]
+
+
+def _rescore_inputs(p, n, N, seed):
+    """Sorted global lines with events exactly on early * N and penalty * N, one line after each, on the
+    first and on the last line (N is chosen so that the products are whole lines), and random factors."""
+    rng = np.random.default_rng(seed)
+    edges = []
+    for thr in (p.early_bonus_threshold, p.penalty_threshold):
+        g = round(thr * N)
+        assert float(g) / N == thr
+        edges += [g, g + 1]
+    gl = np.sort(np.concatenate([rng.integers(0, N, size=n - 6), np.array(edges + [0, N - 1])])).astype(np.int64)
     fac = rng.uniform(0.1, 3.0, size=(n, 7))
     fac[:, 6] = rng.uniform(0, 0.5, size=n)
-    got = K.rescore(torch.from_numpy(gl), torch.from_numpy(fac), N, sp).numpy()
-    ref = np.array([fac[i, 0] * fac[i, 1] * chronological_factor(int(gl[i]), N, p) * fac[i, 3] * fac[i, 4] * fac[i, 5]
-                    * (1.0 - fac[i, 6]) for i in range(n)])
-    np.testing.assert_array_equal(got, ref)
+    return gl, fac
+
+
+def _rescore_ref(gl, fac, N, p, rows):
+    from log_parser_amd.golden import chronological_factor
+    return np.array([fac[i, 0] * fac[i, 1] * chronological_factor(int(gl[i]), N, p) * fac[i, 3] * fac[i, 4] * fac[i, 5]
+                     * (1.0 - fac[i, 6]) for i in rows])
+
+
+def test_rescore_matches_reference_order():
+    from log_parser_amd.engine import Engine
+    for p in _rescore_params():
+        sp = Engine.score_param_tuple(p)
+        n, N = 4000, 12340
+        gl, fac = _rescore_inputs(p, n, N, 7)
+        got = K.rescore(torch.from_numpy(gl), torch.from_numpy(fac), N, sp).numpy()
+        np.testing.assert_array_equal(got, _rescore_ref(gl, fac, N, p, range(n)))
 
 
 @pytest.mark.gpu
@@ -135,3 +158,13 @@ def test_rescore_gpu_equals_cpu(gpu_device):
     a = K.rescore(gl, fac, N, sp)
     b = K.rescore(gl.to(gpu_device), fac.to(gpu_device), N, sp).cpu()
     assert torch.equal(a, b)
+    # both parameter sets with events exactly on early * N and penalty * N: the device equals the host
+    # twin, and both equal the reference's chronological factor in the reference's product order
+    for p in _rescore_params():
+        sp = Engine.score_param_tuple(p)
+        n, N = 20_000, 1_000_000
+        gl, fac = _rescore_inputs(p, n, N, 9)
+        a = K.rescore(torch.from_numpy(gl), torch.from_numpy(fac), N, sp)
+        b = K.rescore(torch.from_numpy(gl).to(gpu_device), torch.from_numpy(fac).to(gpu_device), N, sp).cpu()
+        assert torch.equal(a, b)
+        np.testing.assert_array_equal(b.numpy(), _rescore_ref(gl, fac, N, p, range(n)))
