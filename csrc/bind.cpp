@@ -1186,6 +1186,27 @@ PYBIND11_MODULE(_lpnative, m) {
     py::gil_scoped_release nogil;
     gap_contains_host(T, P<const int64_t>(sig), n, P<uint8_t>(out)); },
         py::arg("tab"), py::arg("sig"), py::arg("n"), py::arg("out"), py::arg("stream"), py::arg("dev"));
+  // ---- lead-up report (leadup.hip): every line's signature, the lines within W lines before an event
+  m.def("lead_sig", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t ev, int64_t ne, int W,
+                       uint64_t sig, uint64_t lead, uint64_t out_line, uint64_t out_sig, int64_t cap, uint64_t cnt,
+                       uint64_t s, bool dev, int per_block) {
+    LeadSigArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.L = L;
+    A.ev = P<const int32_t>(ev); A.ne = ne; A.W = W;
+    A.sig = P<int64_t>(sig); A.lead = P<uint8_t>(lead);
+    A.out_line = P<int32_t>(out_line); A.out_sig = P<int64_t>(out_sig);
+    A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      lead_sig_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    lead_sig_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("ev"), py::arg("ne"),
+        py::arg("window"), py::arg("sig"), py::arg("lead"), py::arg("out_line"), py::arg("out_sig"), py::arg("cap"),
+        py::arg("cnt"), py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

@@ -447,6 +447,31 @@ void gap_contains_dev(const GapTab& T, const int64_t* sig, int64_t n, uint8_t* o
 void gap_contains_host(const GapTab& T, const int64_t* sig, int64_t n, uint8_t* out);
 }  // namespace lp
 
+// ---- lead-up report (leadup.hip): every line's signature, and the lines within W lines before an event
+namespace lp {
+struct LeadSigArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t L;                 // at most 2^31 - 1
+  const int32_t* ev = nullptr;     // [ne] the lines that carry an event: sorted, distinct; null when ne == 0
+  int64_t ne = 0;
+  int W;                     // 1 .. 4096: line x is in the lead-up iff some ev[j] has x < ev[j] <= x + W
+  // outputs: sig[x] = signature bit pattern and lead[x] = 0 / 1 of every line; the lead-up lines
+  // again as (line, signature) pairs, the first `cap` of them; cnt[0] += lead-up lines (all of
+  // them: above cap the caller re-runs, as with novel_sig_dev)
+  int64_t* sig; uint8_t* lead;
+  int32_t* out_line; int64_t* out_sig;
+  int64_t cap;
+  unsigned long long* cnt;   // [1], zeroed by the caller
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from L.
+// GPU: the pairs come in no particular order
+void lead_sig_dev(const LeadSigArgs& A, uint64_t stream, int per_block = 0);
+// appends in line order
+void lead_sig_host(const LeadSigArgs& A);
+}  // namespace lp
+
 // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
 namespace lp {
 // out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN

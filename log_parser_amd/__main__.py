@@ -26,6 +26,11 @@
                                                the stack traces of a log grouped by their frames and
                                                causes: how often, where first, the root cause, and
                                                whether an event lies on them (JSON)
+  leadup    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--window N] [--top N]
+            [--order share|count|first] [--min-count N]
+                                               the line templates that lie within a window of lines
+                                               before the events of a log more often than elsewhere:
+                                               what the log said just before each failure (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -156,6 +161,21 @@ def cmd_traces(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_leadup(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    kw = {"window": args.window, "top": args.top, "order": args.order, "min_count": args.min_count}
+    try:
+        if args.stream:
+            rep = lp.leadup_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.leadup_file(args.file, **kw)
+    except ValueError as e:                 # a window or a minimum count out of range
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -211,11 +231,24 @@ def main(argv: Optional[List[str]] = None) -> int:
     r.add_argument("--order", choices=("count", "first"), default="count",
                    help="most frequent first (default), or in order of first appearance")
     r.add_argument("--unexplained-only", action="store_true", help="list only the groups no event lies on")
+    u = sub.add_parser("leadup", help="line templates of a log file that precede its events more often than elsewhere")
+    u.add_argument("file")
+    _library_options(u)
+    u.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    u.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    u.add_argument("--window", type=int, default=50, metavar="N", help="lines before an event that count (default 50)")
+    u.add_argument("--top", type=int, default=20, help="groups reported (default 20)")
+    u.add_argument("--order", choices=("share", "count", "first"), default="share",
+                   help="largest share of the template's lines first (default), most frequent first, "
+                        "or in order of first appearance")
+    u.add_argument("--min-count", type=int, default=2, metavar="N",
+                   help="list only the groups with at least N lead-up lines (default 2)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
-            "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces}[args.cmd](args, cfg)
+            "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
+            "leadup": cmd_leadup}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

@@ -38,6 +38,7 @@ SOURCES = [
     ("kernels/gaps.hip", "hip"),
     ("kernels/gap_table.hip", "hip"),
     ("kernels/novelty.hip", "hip"),
+    ("kernels/leadup.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),

@@ -28,6 +28,10 @@ to embedders, with what an in-process user needs beyond one call at a time:
 * ``traces`` / ``traces_file``: the stack traces of a log grouped by their frames and causes --
   how often, where first, the root cause, whether an event explains them; ``traces_stream`` /
   ``traces_resident`` for one log too large for one piece;
+* ``leadup`` / ``leadup_file``: the line templates that lie within a window of lines before the
+  events of a log more often than elsewhere -- what the log said just before each failure;
+  ``leadup_stream`` / ``leadup_resident`` for one log too large for one piece,
+  ``leadup_accumulator`` for a log that arrives over time;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -358,6 +362,62 @@ class LogParser:
         acc = self._trace_accumulator()
         acc.add_resident(resident)
         return acc.report(top, order, unexplained_only)
+
+    # ---- lead-up report -----------------------------------------------------------------------
+    def leadup(self, logs, window: int = 50, top: Optional[int] = 20, order: str = "share", min_count: int = 2) -> dict:
+        """What does one document (str or bytes) say just before its failures that it does not
+        usually say? A line is in the lead-up when an event lies on one of the ``window`` (1..4096)
+        lines after it. The lines are grouped by template: per group its lines in the lead-up
+        (``count``), all its lines (``total``), ``share`` = count / total, ``lift`` = share against
+        the lead-up's share of all lines, its first lead-up line and that line as the example.
+        Listed are the groups with ``count >= min_count``: ``order="share"`` by share, then count;
+        ``"count"``: most frequent first; ``"first"``: in order of first appearance; ``top=None``:
+        every group. ``Engine.leadup_bytes``; ``golden.leadup`` is the specification; the frequency
+        window is not touched."""
+        from .leadup import check_args
+        check_args(window, order, min_count)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("leadup"):
+            return self.engine.leadup_bytes(logs, window=window, top=top, order=order, min_count=min_count)
+
+    def leadup_file(self, path: str, window: int = 50, top: Optional[int] = 20, order: str = "share",
+                    min_count: int = 2) -> dict:
+        """``leadup`` of a log file, read as ONE document whatever its size."""
+        from .leadup import check_args
+        check_args(window, order, min_count)
+        with open(path, "rb") as f:
+            return self.leadup(f.read(), window=window, top=top, order=order, min_count=min_count)
+
+    def leadup_accumulator(self, window: int = 50):
+        """A ``leadup.LeadupAccumulator`` on this parser's engine for a log that arrives over time
+        (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then ``report``);
+        each of its calls runs under the batcher guard and the lock of ``leadup``."""
+        from .leadup import LeadupAccumulator
+        with self._engine_guard("leadup"):
+            return LeadupAccumulator(self.engine, window, guard=lambda: self._engine_guard("leadup"))
+
+    def leadup_stream(self, src_or_path, chunk_bytes: Optional[int] = None, window: int = 50, top: Optional[int] = 20,
+                      order: str = "share", min_count: int = 2) -> dict:
+        """``leadup`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The tail of a chunk
+        can lie in the lead-up of the next chunk's event; the report is exactly the one-document
+        report, whatever the chunk size."""
+        from .leadup import check_args
+        check_args(window, order, min_count)
+        acc = self.leadup_accumulator(window)
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(top, order, min_count)
+
+    def leadup_resident(self, resident, window: int = 50, top: Optional[int] = 20, order: str = "share",
+                        min_count: int = 2) -> dict:
+        """``leadup`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        from .leadup import check_args
+        check_args(window, order, min_count)
+        acc = self.leadup_accumulator(window)
+        acc.add_resident(resident)
+        return acc.report(top, order, min_count)
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

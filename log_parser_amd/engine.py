@@ -861,6 +861,22 @@ class Engine:
         from .novelty import novelty_document
         return novelty_document(self, text, n, data, baseline, top, order, errors_only)
 
+    # ------------------------------------------------------------------ lead-up report
+    def leadup_bytes(self, data: bytes, window: int = 50, top: Optional[int] = 20, order: str = "share",
+                     min_count: int = 2) -> dict:
+        """Which line templates of one document lie within ``window`` lines before an event more
+        often than elsewhere? (leadup.py; ``golden.leadup`` is the specification.) Nothing is scored
+        and the frequency window is not touched."""
+        data = bytes(data)
+        text, n = self.stage_text(data)
+        return self.leadup_document(text, n, data, window=window, top=top, order=order, min_count=min_count)
+
+    def leadup_document(self, text, n: int, data: bytes, window: int = 50, top: Optional[int] = 20,
+                        order: str = "share", min_count: int = 2) -> dict:
+        """``leadup_bytes`` of a staged document: ``text`` = ``stage_text(data)``'s buffer."""
+        from .leadup import leadup_document
+        return leadup_document(self, text, n, data, window, top, order, min_count)
+
     # ------------------------------------------------------------------ trace report
     def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
                      unexplained_only: bool = False) -> dict:

@@ -495,6 +495,67 @@ def novelty(logs, baseline_docs, pattern_sets: List[PatternSet], params: Scoring
 
 
 # ---------------------------------------------------------------------------------------------
+# Lead-up report (an extra, as the gap report): what does a log say just before its failures that
+# it does not usually say? A line is *in the lead-up* when an event of ``analyze`` lies on one of
+# the ``window`` lines after it. The templates of these lines are weighed against all the lines of
+# the same template. This function is the specification of ``log_parser_amd/leadup.py`` and of the
+# kernel that signs every line and marks the lead-up in one pass (csrc/kernels/leadup.hip).
+#
+# Known limits are the signatures': two templates may share a 64-bit signature, and only the first
+# ``SIG_MAX_BYTES`` bytes of a line count.
+
+LEAD_MAX_WINDOW = 4096
+
+
+def leadup(logs, pattern_sets: List[PatternSet], params: ScoringParams, window: int = 50, top: Optional[int] = 20,
+           order: str = "share", min_count: int = 2) -> dict:
+    """The lead-up report of ``logs``. ``E``: the lines that carry at least one event. A line ``x``
+    is in the lead-up iff some ``e`` in ``E`` has ``x < e <= x + window`` -- an event line is not in
+    its own lead-up, but can be in a later event's. Lines are grouped by ``line_signature``; per
+    group ``total`` (its lines in the log), ``count`` (those in the lead-up), ``share`` = count /
+    total, ``lift`` = share against the lead-up's share of all lines, and its first lead-up line.
+    Listed are the groups with ``count >= min_count``: ``order="share"`` by (-share, -count, first
+    line), ``"count"`` by (-count, first line), ``"first"`` by first line."""
+    if order not in ("share", "count", "first"):
+        raise ValueError("order must be 'share', 'count' or 'first'")
+    if not 1 <= window <= LEAD_MAX_WINDOW:
+        raise ValueError("window must be 1..%d" % LEAD_MAX_WINDOW)
+    if min_count < 1:
+        raise ValueError("min_count must be at least 1")
+    logs = _as_text(logs)
+    res = analyze(logs, pattern_sets, params, FrequencyTracker(params))
+    lines = split_lines(logs)
+    E = sorted({e["lineNumber"] - 1 for e in res["events"]})
+    lead = [False] * len(lines)
+    for e in E:
+        for x in range(max(0, e - window), e):
+            lead[x] = True
+    groups: Dict[int, list] = {}                # signature -> [total, count, first lead-up line, raw of it]
+    for i, line in enumerate(lines):
+        raw = line.encode("utf-8", errors="surrogateescape")
+        g = groups.setdefault(line_signature(raw), [0, 0, None, None])
+        g[0] += 1
+        if lead[i]:
+            g[1] += 1
+            if g[2] is None:
+                g[2], g[3] = i, raw
+    n_lead = sum(lead)
+    listed = [kv for kv in groups.items() if kv[1][1] >= min_count]
+    listed.sort(key={"share": lambda kv: (-(kv[1][1] / kv[1][0]), -kv[1][1], kv[1][2]),
+                     "count": lambda kv: (-kv[1][1], kv[1][2]),
+                     "first": lambda kv: kv[1][2]}[order])
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    return {"totalLines": len(lines), "events": len(res["events"]), "eventLines": len(E), "window": window,
+            "leadLines": n_lead, "templates": sum(1 for g in groups.values() if g[1]),
+            "top": [{"count": c, "total": t, "share": c / t, "lift": (c * len(lines)) / (t * n_lead),
+                     "firstLine": i + 1, "signature": "%016x" % sig,
+                     "template": line_template(raw).decode("utf-8", errors="replace"),
+                     "example": raw.decode("utf-8", errors="replace")}
+                    for sig, (t, c, i, raw) in listed]}
+
+
+# ---------------------------------------------------------------------------------------------
 # Log timeline (an extra: the reference reads no time a log line carries). When did the lines, the
 # error lines and the events of a log happen? These functions are the specification of
 # ``Engine.timeline_bytes`` and of the timestamp kernel (csrc/kernels/ts_core.h).

@@ -1100,6 +1100,51 @@ def novel_lines(text, line_start, line_len, table: GapTable, feat: Optional[torc
 
 
 # ---------------------------------------------------------------------------------------------
+# lead-up report (csrc/kernels/leadup.hip): every line's signature, the lines shortly before an event
+
+LD_MAX_LINES = 2048         # lines per block of k_lead_sig at most
+LD_MAX_WINDOW = 4096        # lines before an event at most
+
+
+def lead_lines(text, line_start, line_len, ev: Optional[torch.Tensor], window: int, cap: Optional[int] = None,
+               per_block: int = 0):
+    """The signature of every line, and the lines in the lead-up of an event: (sig int64[L], lead
+    uint8[L], line int32[n], pair_sig int64[n], n). ``ev``: the lines that carry an event (int32,
+    sorted and distinct, counted as the lines are; empty or None: no events). Line x is in the
+    lead-up iff some e of ``ev`` has ``x < e <= x + window``; the n lead-up lines come again as
+    (line, signature) pairs. One pass over the text (k_lead_sig) with the capacity protocol of
+    ``novel_lines``; ``cap=None`` starts well below L -- the lead-up of a mostly healthy log is
+    short. ``per_block``: lines per block instead of the size the launch picks (tests). GPU: the
+    pairs come in no particular order; CPU: in line order."""
+    dev = text.device
+    L = line_start.numel()
+    if not 1 <= window <= LD_MAX_WINDOW:
+        raise ValueError("lead_lines: window must be 1..%d" % LD_MAX_WINDOW)
+    if ev is not None and (ev.dtype != torch.int32 or ev.dim() != 1 or not ev.is_contiguous() or ev.device != dev):
+        raise ValueError("lead_lines: ev must be contiguous int32[ne] on the text's device")
+    if per_block and not 0 < per_block <= LD_MAX_LINES:
+        raise ValueError("lead_lines: per_block must be 1..%d" % LD_MAX_LINES)
+    sig = torch.empty(L, dtype=torch.int64, device=dev)
+    lead = torch.empty(L, dtype=torch.uint8, device=dev)
+    if L == 0:
+        return (sig, lead, torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev), 0)
+    ne = 0 if ev is None else ev.numel()
+    cap = max(1024, L // 16) if cap is None else max(0, int(cap))
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_sig = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        N.lead_sig(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L,
+                   _p(ev) if ne else 0, ne, int(window), sig.data_ptr(), lead.data_ptr(), out_line.data_ptr(),
+                   out_sig.data_ptr(), cap, cnt.data_ptr(), _s(text), text.is_cuda, per_block)
+        n = int(cnt.item())
+        if n <= cap:
+            return sig, lead, out_line[:n], out_sig[:n], n
+        cap = n
+
+
+# ---------------------------------------------------------------------------------------------
 # log timeline (csrc/kernels/timeline.hip): the timestamp of every line, counts per time bucket
 
 TS_NONE = -(1 << 63)        # a line without a stamp / without an effective time (csrc/kernels/ts_core.h)
