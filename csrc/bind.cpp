@@ -1207,6 +1207,28 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("L"), py::arg("ev"), py::arg("ne"),
         py::arg("window"), py::arg("sig"), py::arg("lead"), py::arg("out_line"), py::arg("out_sig"), py::arg("cap"),
         py::arg("cnt"), py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  // ---- correlation report (correlate.hip): the id-like tokens of lines as (line, key) pairs
+  m.def("line_keys", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, uint64_t sel, int64_t n,
+                        py::object tab, int min_len, uint64_t out_line, uint64_t out_key, uint64_t hit, int64_t cap,
+                        uint64_t cnt, uint64_t s, bool dev, int per_block) {
+    KeyLinesArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.nl = nl;
+    A.sel = P<const int32_t>(sel); A.n = n;
+    A.tab = tab.is_none() ? GapTab{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0} : gt_from(tab.cast<py::tuple>());
+    A.min_len = min_len;
+    A.out_line = P<int32_t>(out_line); A.out_key = P<int64_t>(out_key); A.hit = P<uint8_t>(hit);
+    A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      line_keys_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    line_keys_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sel"), py::arg("n"),
+        py::arg("tab"), py::arg("min_len"), py::arg("out_line"), py::arg("out_key"), py::arg("hit"), py::arg("cap"),
+        py::arg("cnt"), py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

@@ -472,6 +472,33 @@ void lead_sig_dev(const LeadSigArgs& A, uint64_t stream, int per_block = 0);
 void lead_sig_host(const LeadSigArgs& A);
 }  // namespace lp
 
+// ---- correlation report (correlate.hip): the id-like tokens of lines as (line, key) pairs
+namespace lp {
+struct KeyLinesArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t nl;                // lines of ls / ll, at most 2^31 - 1
+  const int32_t* sel = nullptr;    // [n] item i walks line sel[i] (0 <= sel[i] < nl); null: line i
+  int64_t n;                 // items walked: nl without sel
+  GapTab tab;                // tab.key null: every key is emitted; else only the keys it holds (only read)
+  int min_len;               // 4 .. 64: bytes of a key token at least (key_core.h)
+  // outputs: the keys of every walked line (its first 8 distinct ones, then the table's filter) as
+  // (line number, key bit pattern) pairs, the first `cap` of them; hit[i] = 0 / 1: item i emitted
+  // a pair; cnt[0] += pairs (all of them: above cap the caller re-runs, as with lead_sig_dev),
+  // cnt[1] += items with at least one pair
+  int32_t* out_line; int64_t* out_key;
+  uint8_t* hit;
+  int64_t cap;
+  unsigned long long* cnt;   // [2], zeroed by the caller
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from n.
+// GPU: the pairs come in no particular order
+void line_keys_dev(const KeyLinesArgs& A, uint64_t stream, int per_block = 0);
+// appends in item order, the keys of a line in byte order
+void line_keys_host(const KeyLinesArgs& A);
+}  // namespace lp
+
 // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
 namespace lp {
 // out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN

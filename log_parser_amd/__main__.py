@@ -31,6 +31,11 @@
                                                the line templates that lie within a window of lines
                                                before the events of a log more often than elsewhere:
                                                what the log said just before each failure (JSON)
+  correlate FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--min-length N]
+            [--order events|lines|first] [--min-lines N] [--max-share F] [--top N]
+                                               the ids on the event lines of a log (request ids,
+                                               trace ids, pod hashes, addresses) followed through
+                                               the log: which other lines hold them (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -176,6 +181,22 @@ def cmd_leadup(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_correlate(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    kw = {"min_len": args.min_length, "top": args.top, "order": args.order, "min_lines": args.min_lines,
+          "max_share": args.max_share}
+    try:
+        if args.stream:
+            rep = lp.correlate_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.correlate_file(args.file, **kw)
+    except ValueError as e:                 # a length, a count or a share out of range
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -243,12 +264,25 @@ def main(argv: Optional[List[str]] = None) -> int:
                         "or in order of first appearance")
     u.add_argument("--min-count", type=int, default=2, metavar="N",
                    help="list only the groups with at least N lead-up lines (default 2)")
+    c = sub.add_parser("correlate", help="the ids on the event lines of a log file, followed through the log")
+    c.add_argument("file")
+    _library_options(c)
+    c.add_argument("--stream", action="store_true", help="the file processed in chunks, read twice (same report)")
+    c.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    c.add_argument("--min-length", type=int, default=8, metavar="N", help="bytes of an id at least (4..64, default 8)")
+    c.add_argument("--top", type=int, default=20, help="ids reported (default 20)")
+    c.add_argument("--order", choices=("events", "lines", "first"), default="events",
+                   help="most event lines first (default), most lines first, or in order of the first event line")
+    c.add_argument("--min-lines", type=int, default=2, metavar="N",
+                   help="list only the ids on at least N lines (default 2)")
+    c.add_argument("--max-share", type=float, default=0.25, metavar="F",
+                   help="drop the ids on more than this share of all lines (default 0.25)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
-            "leadup": cmd_leadup}[args.cmd](args, cfg)
+            "leadup": cmd_leadup, "correlate": cmd_correlate}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

@@ -39,6 +39,7 @@ SOURCES = [
     ("kernels/gap_table.hip", "hip"),
     ("kernels/novelty.hip", "hip"),
     ("kernels/leadup.hip", "hip"),
+    ("kernels/correlate.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),

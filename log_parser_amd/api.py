@@ -32,6 +32,10 @@ to embedders, with what an in-process user needs beyond one call at a time:
   events of a log more often than elsewhere -- what the log said just before each failure;
   ``leadup_stream`` / ``leadup_resident`` for one log too large for one piece,
   ``leadup_accumulator`` for a log that arrives over time;
+* ``correlate`` / ``correlate_file``: the ids (request ids, trace ids, pod hashes, addresses) on
+  the event lines of a log, followed through the whole log -- ``golden.correlate``;
+  ``correlate_stream`` / ``correlate_resident`` for one log too large for one piece (the source
+  is walked twice);
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -418,6 +422,59 @@ class LogParser:
         acc = self.leadup_accumulator(window)
         acc.add_resident(resident)
         return acc.report(top, order, min_count)
+
+    # ---- correlation report ------------------------------------------------------------------
+    def correlate(self, logs, min_len: int = 8, top: Optional[int] = 20, order: str = "events", min_lines: int = 2,
+                  max_share: float = 0.25) -> dict:
+        """What else does one document (str or bytes) say about the ids on its failing lines? A
+        *key* is an id-like token of a line: a ``[0-9A-Za-z]`` run of ``min_len`` (4..64) to 64
+        bytes that holds a digit, letters lowered -- a request id, a trace id, a pod hash, an
+        address. Per key of an event line: the event lines holding it (``eventLines``), all lines
+        holding it (``lines``), ``share`` = eventLines / lines, its first and last line, its first
+        event line, and its first line as the example. Dropped are the keys on fewer than
+        ``min_lines`` lines (an id seen only on its own event line) and on more than ``max_share``
+        of all lines (a host name on every line). ``order="events"``: most event lines first, then
+        most lines; ``"lines"``: most lines first; ``"first"``: in order of the first event line;
+        ``top=None``: every key. ``Engine.correlate_bytes``; ``golden.correlate`` is the
+        specification; the frequency window is not touched."""
+        from .correlate import check_args
+        check_args(min_len, order, min_lines, max_share)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("correlate"):
+            return self.engine.correlate_bytes(logs, min_len=min_len, top=top, order=order, min_lines=min_lines,
+                                               max_share=max_share)
+
+    def correlate_file(self, path: str, min_len: int = 8, top: Optional[int] = 20, order: str = "events",
+                       min_lines: int = 2, max_share: float = 0.25) -> dict:
+        """``correlate`` of a log file, read as ONE document whatever its size."""
+        from .correlate import check_args
+        check_args(min_len, order, min_lines, max_share)
+        with open(path, "rb") as f:
+            return self.correlate(f.read(), min_len=min_len, top=top, order=order, min_lines=min_lines,
+                                  max_share=max_share)
+
+    def correlate_stream(self, src_or_path, chunk_bytes: Optional[int] = None, min_len: int = 8,
+                         top: Optional[int] = 20, order: str = "events", min_lines: int = 2,
+                         max_share: float = 0.25) -> dict:
+        """``correlate`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The report walks its
+        source TWICE -- first with the matchers for the ids of the event lines, then without them
+        for every line that holds one of those ids -- so the source is uploaded twice and must not
+        change in between; memory is bounded by the ids of the event lines, not by the ids of the
+        log. The report is exactly the one-document report, whatever the chunk size."""
+        from .correlate import check_args, correlate_stream
+        check_args(min_len, order, min_lines, max_share)
+        with _source(src_or_path) as src, self._engine_guard("correlate"):
+            return correlate_stream(self.engine, src, chunk_bytes, min_len, top, order, min_lines, max_share)
+
+    def correlate_resident(self, resident, min_len: int = 8, top: Optional[int] = 20, order: str = "events",
+                           min_lines: int = 2, max_share: float = 0.25) -> dict:
+        """``correlate`` of a log held in HBM (``load_resident``), read in place twice."""
+        from .correlate import check_args, correlate_stream
+        check_args(min_len, order, min_lines, max_share)
+        with self._engine_guard("correlate"):
+            return correlate_stream(self.engine, resident, None, min_len, top, order, min_lines, max_share)
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

@@ -877,6 +877,23 @@ class Engine:
         from .leadup import leadup_document
         return leadup_document(self, text, n, data, window, top, order, min_count)
 
+    # ------------------------------------------------------------------ correlation report
+    def correlate_bytes(self, data: bytes, min_len: int = 8, top: Optional[int] = 20, order: str = "events",
+                        min_lines: int = 2, max_share: float = 0.25) -> dict:
+        """Which ids do the event lines of one document carry, and which other lines hold them?
+        (correlate.py; ``golden.correlate`` is the specification.) Nothing is scored and the
+        frequency window is not touched."""
+        data = bytes(data)
+        text, n = self.stage_text(data)
+        return self.correlate_document(text, n, data, min_len=min_len, top=top, order=order, min_lines=min_lines,
+                                       max_share=max_share)
+
+    def correlate_document(self, text, n: int, data: bytes, min_len: int = 8, top: Optional[int] = 20,
+                           order: str = "events", min_lines: int = 2, max_share: float = 0.25) -> dict:
+        """``correlate_bytes`` of a staged document: ``text`` = ``stage_text(data)``'s buffer."""
+        from .correlate import correlate_document
+        return correlate_document(self, text, n, data, min_len, top, order, min_lines, max_share)
+
     # ------------------------------------------------------------------ trace report
     def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
                      unexplained_only: bool = False) -> dict:

@@ -556,6 +556,113 @@ def leadup(logs, pattern_sets: List[PatternSet], params: ScoringParams, window: 
 
 
 # ---------------------------------------------------------------------------------------------
+# Correlation report (an extra, as the gap report): the failing line carries a request id, a trace
+# id, a pod hash or an address -- what else did the log say about that id? The lead-up is
+# positional; in a concurrent service the lines of the failed request are interleaved with
+# everyone else's, and this report follows the id instead. These functions are the specification
+# of ``log_parser_amd/correlate.py`` and of the key kernel (csrc/kernels/key_core.h, correlate.hip).
+#
+# Known limits: two tokens may share a 64-bit key; only the first ``SIG_MAX_BYTES`` bytes of a line
+# and its first ``KEY_PER_LINE`` distinct keys count; an id with ``-`` or ``_`` inside is several
+# tokens (a UUID gives two keys, its 8-byte and its 12-byte group).
+
+KEY_MIN_LEN = 4
+KEY_MAX_LEN = 64
+KEY_PER_LINE = 8
+
+
+def line_key_tokens(line: bytes, min_len: int = 8) -> List[tuple]:
+    """[(key, lowered token)] of a line: of its first ``SIG_MAX_BYTES`` bytes (a run still open
+    there ends there), every maximal ``[0-9A-Za-z]`` run of ``min_len .. KEY_MAX_LEN`` bytes that
+    holds a digit is a key token; its key is FNV-1a-64 of the token with ASCII letters lowered.
+    The first ``KEY_PER_LINE`` distinct keys in byte order; a further one is ignored."""
+    out, seen = [], set()
+    for m in _TOKEN.finditer(bytes(line[:SIG_MAX_BYTES])):
+        t = m.group()
+        if not min_len <= len(t) <= KEY_MAX_LEN or not _DIGIT.search(t):
+            continue
+        t = t.lower()
+        k = fnv1a64(t)
+        if k in seen:
+            continue
+        if len(out) == KEY_PER_LINE:
+            break
+        seen.add(k)
+        out.append((k, t))
+    return out
+
+
+def line_keys(line: bytes, min_len: int = 8) -> List[int]:
+    """The keys of a line (``line_key_tokens``) as unsigned 64-bit numbers."""
+    return [k for k, _ in line_key_tokens(line, min_len)]
+
+
+def correlate_check_args(min_len: int = 8, order: str = "events", min_lines: int = 2, max_share: float = 0.25) -> None:
+    if order not in ("events", "lines", "first"):
+        raise ValueError("order must be 'events', 'lines' or 'first'")
+    if not KEY_MIN_LEN <= min_len <= KEY_MAX_LEN:
+        raise ValueError("min_len must be %d..%d" % (KEY_MIN_LEN, KEY_MAX_LEN))
+    if min_lines < 1:
+        raise ValueError("min_lines must be at least 1")
+    if not 0.0 < max_share <= 1.0:
+        raise ValueError("max_share must be in (0, 1]")
+
+
+def correlate(logs, pattern_sets: List[PatternSet], params: ScoringParams, min_len: int = 8,
+              top: Optional[int] = 20, order: str = "events", min_lines: int = 2, max_share: float = 0.25) -> dict:
+    """The correlation report of ``logs``. The *event keys* are the keys (``line_keys``) of the
+    lines that carry an event of ``analyze``. Per event key: ``eventLines`` (distinct event lines
+    holding it), ``lines`` (all lines holding it, event lines included), ``share`` = eventLines /
+    lines, its first and last line, its first event line, the lowered token and the first line as
+    the example. Dropped are the keys with ``lines < min_lines`` (an id seen only on its own event
+    line correlates nothing) and those with ``lines > max_share * totalLines`` (a host name on
+    every line correlates everything). ``order="events"``: by (-eventLines, -lines, first line,
+    key); ``"lines"``: (-lines, -eventLines, first line, key); ``"first"``: (first event line,
+    key). ``keys`` counts the event keys before the filters, ``keyLines`` the lines that hold at
+    least one."""
+    correlate_check_args(min_len, order, min_lines, max_share)
+    logs = _as_text(logs)
+    res = analyze(logs, pattern_sets, params, FrequencyTracker(params))
+    raws = [line.encode("utf-8", errors="surrogateescape") for line in split_lines(logs)]
+    E = sorted({e["lineNumber"] - 1 for e in res["events"]})
+    groups: Dict[int, list] = {}        # key -> [event lines, first event line, lines, first line, last line]
+    for e in E:
+        for k in line_keys(raws[e], min_len):
+            groups.setdefault(k, [0, e, 0, None, None])[0] += 1
+    key_lines = 0
+    for i, raw in enumerate(raws):
+        held = [k for k in line_keys(raw, min_len) if k in groups] if groups else []
+        key_lines += bool(held)
+        for k in held:
+            g = groups[k]
+            g[2] += 1
+            if g[3] is None:
+                g[3] = i
+            g[4] = i
+    listed = [kv for kv in groups.items() if min_lines <= kv[1][2] <= max_share * len(raws)]
+    listed.sort(key={"events": lambda kv: (-kv[1][0], -kv[1][2], kv[1][3], kv[0]),
+                     "lines": lambda kv: (-kv[1][2], -kv[1][0], kv[1][3], kv[0]),
+                     "first": lambda kv: (kv[1][1], kv[0])}[order])
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    return {"totalLines": len(raws), "events": len(res["events"]), "eventLines": len(E), "minLength": min_len,
+            "keys": len(groups), "keyLines": key_lines,
+            "top": [correlate_row(k, ne, fe, n, f, last, raws[f], min_len) for k, (ne, fe, n, f, last) in listed]}
+
+
+def correlate_row(key: int, event_lines: int, first_event: int, lines: int, first: int, last: int, raw: bytes,
+                  min_len: int) -> dict:
+    """One row of the report from its numbers (lines 0-based) and the first line holding the key:
+    the token is the one of that line whose hash is the key. ValueError if none has it."""
+    tok = dict(line_key_tokens(raw, min_len)).get(key)
+    if tok is None:
+        raise ValueError("correlate: line %d does not hold the key %016x" % (first + 1, key))
+    return {"key": tok.decode("ascii"), "eventLines": event_lines, "lines": lines, "share": event_lines / lines,
+            "firstLine": first + 1, "lastLine": last + 1, "firstEventLine": first_event + 1,
+            "signature": "%016x" % key, "example": raw.decode("utf-8", errors="replace")}
+
+
+# ---------------------------------------------------------------------------------------------
 # Log timeline (an extra: the reference reads no time a log line carries). When did the lines, the
 # error lines and the events of a log happen? These functions are the specification of
 # ``Engine.timeline_bytes`` and of the timestamp kernel (csrc/kernels/ts_core.h).

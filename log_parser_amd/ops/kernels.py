@@ -1145,6 +1145,60 @@ def lead_lines(text, line_start, line_len, ev: Optional[torch.Tensor], window: i
 
 
 # ---------------------------------------------------------------------------------------------
+# correlation report (csrc/kernels/correlate.hip): the id-like tokens of lines as (line, key) pairs
+
+KL_MAX_LINES = 2048         # lines per block of k_line_keys at most
+KEY_MIN_LEN, KEY_MAX_LEN = 4, 64    # bounds of ``min_len``; the longest key token (csrc/kernels/key_core.h)
+KEY_PER_LINE = 8            # distinct keys of a line at most
+
+
+def line_keys(text, line_start, line_len, sel: Optional[torch.Tensor] = None, table: Optional[GapTable] = None,
+              min_len: int = 8, cap: Optional[int] = None, per_block: int = 0):
+    """The keys (``golden.line_keys``) of lines as pairs: (line int32[n], key int64[n], hit
+    uint8[walked], (n, walked lines with at least one pair)). ``sel`` (int32, values in [0, L)):
+    item i walks line ``sel[i]`` and ``hit[i]`` speaks of it; None: every line. ``table``: only
+    the keys it holds are emitted (the filter comes after the line's first ``KEY_PER_LINE``
+    distinct keys are chosen, so a line means the same in every pass). One pass over the text
+    (k_line_keys) with the capacity protocol of ``lead_lines``. ``per_block``: lines per block
+    instead of the size the launch picks (tests). GPU: the pairs come in no particular order;
+    CPU: in item order, the keys of a line in byte order."""
+    dev = text.device
+    L = line_start.numel()
+    if not KEY_MIN_LEN <= min_len <= KEY_MAX_LEN:
+        raise ValueError("line_keys: min_len must be %d..%d" % (KEY_MIN_LEN, KEY_MAX_LEN))
+    if sel is not None:
+        if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous() or sel.device != dev:
+            raise ValueError("line_keys: sel must be contiguous int32[n] on the text's device")
+        if sel.numel():
+            lo, hi = torch.aminmax(sel)
+            if int(lo) < 0 or int(hi) >= L:
+                raise ValueError("line_keys: sel names a line outside [0, %d)" % L)
+    if table is not None and table.device != dev:
+        raise ValueError("line_keys: the table lives on %s, the text on %s" % (table.device, dev))
+    if per_block and not 0 < per_block <= KL_MAX_LINES:
+        raise ValueError("line_keys: per_block must be 1..%d" % KL_MAX_LINES)
+    n = L if sel is None else sel.numel()
+    hit = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev), hit,
+                (0, 0))
+    # a re-run costs a whole pass over the text, a pair 12 bytes: start generously. Without a table a
+    # line of a service log holds an id or two; with one, the event keys' lines are a fraction of the log
+    cap = (max(1024, n // 4) if table is not None else max(1024, 2 * n)) if cap is None else max(0, int(cap))
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_key = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        N.line_keys(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, _p(sel), n,
+                    None if table is None else table._tab(), int(min_len), out_line.data_ptr(), out_key.data_ptr(),
+                    hit.data_ptr(), cap, cnt.data_ptr(), _s(text), text.is_cuda, per_block)
+        m, lines = cnt.tolist()
+        if m <= cap:
+            return out_line[:m], out_key[:m], hit, (m, lines)
+        cap = m
+
+
+# ---------------------------------------------------------------------------------------------
 # log timeline (csrc/kernels/timeline.hip): the timestamp of every line, counts per time bucket
 
 TS_NONE = -(1 << 63)        # a line without a stamp / without an effective time (csrc/kernels/ts_core.h)

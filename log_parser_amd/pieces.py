@@ -8,7 +8,9 @@ loop over pieces; what differs between the two kinds of source stays in here:
 * :func:`stream_pieces`: a bytes-like source or a ``ResidentLog`` is ONE document in the chunks of
   ``parallel.stream.document_chunks`` -- line-aligned, with ``lib.halo`` lines of the neighbours on
   either side, split by ``K.split_chunk_lines`` (nothing trimmed). ``prepare`` emits the events of
-  a chunk's own lines only, and the piece is cut down to those lines; no halo leaves this module.
+  a chunk's own lines only, and the piece is cut down to those lines; no halo leaves this module;
+* :func:`stream_lines`: the same chunks and the same lines without the matchers, for a report that
+  walks its source a second time (correlate.py).
 
 An event of a neighbouring piece can still concern a line of this one: such carries belong to the
 report (``line_base`` and ``last`` are for them). Nothing is scored, no frequency window touched.
@@ -107,4 +109,23 @@ def _chunk_pieces(eng: Engine, chunks, line_base: int) -> Iterator[Piece]:
                            split_trim=False)
         yield Piece(eng, text, ls[own_lo:own_hi], ll[own_lo:own_hi], prep.ev_line - own_lo, prep.ev_pat, line_base,
                     last)
+        line_base += own_hi - own_lo
+
+
+@contextlib.contextmanager
+def stream_lines(eng: Engine, src, chunk_bytes: Optional[int] = None, line_base: int = 0):
+    """``with stream_lines(eng, src) as walk: for text, ls, ll, base in walk: ...`` -- the lines of
+    the source of ``stream_pieces`` WITHOUT the matchers: of every chunk its own lines (the halo
+    lines cut off) as their index in ``text`` and the document number ``base`` of the first. The
+    same chunks and the same lines as the pieces, for a report that walks its source a second
+    time and needs no events there (correlate.py)."""
+    with contextlib.closing(document_chunks(eng, src, chunk_bytes)) as chunks:
+        yield _chunk_lines(chunks, line_base)
+
+
+def _chunk_lines(chunks, line_base: int):
+    for text, n, lh, rh, _host, _last in chunks:
+        ls, ll = K.split_chunk_lines(text, n)
+        own_lo, own_hi = lh, ls.numel() - rh
+        yield text, ls[own_lo:own_hi], ll[own_lo:own_hi], line_base
         line_base += own_hi - own_lo

@@ -8,7 +8,7 @@ pattern triggers are planted at a controlled rate.
 from __future__ import annotations
 
 import random
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 from ..models.schema import PatternSet
 
@@ -386,6 +386,56 @@ def templated_log(n_lines: int, templates: List[str], seed: int = 0, crlf_rate: 
         parts.append(t % ((i // 60) % 60, i % 60, i % 1000, *(rng.randrange(1, 1 << 20) for _ in range(nf))))
         parts.append("\r\n" if rng.random() < crlf_rate else "\n")
     return "".join(parts)
+
+
+CORRELATED_FAIL = "request aborted: upstream deadline exceeded"     # what the last line of a failing request says
+
+
+def correlated_log(n_lines: int, templates: List[str], n_requests: int, seed: int = 0, fail_rate: float = 0.25,
+                   crlf_rate: float = 0.0) -> Tuple[str, Dict[str, List[int]]]:
+    """A ``templated_log`` whose lines carry a `` rid=<16 hex>`` field: the ids come from a pool of
+    ``n_requests`` requests, each spanning a random stretch of the log (about eight are under way
+    at any line, so their lines interleave), and a line takes the id of one of the requests under
+    way, or none where there is none. About ``fail_rate`` of the requests *fail*: the last line of
+    their stretch is theirs and is an ERROR line that says ``CORRELATED_FAIL``; so is the first,
+    so that a failing request has at least two lines. Returns (text, {id of a failing request:
+    its lines, 0-based and ascending, the failing line last}) -- known by construction."""
+    rng = random.Random(seed)
+    lines = templated_log(n_lines, templates, seed=seed).split("\n")[:n_lines]
+    span = max(4, 16 * n_lines // max(1, n_requests))
+    ids, reqs = set(), []
+    forced: Dict[int, int] = {}                     # line -> request that owns it whatever else is under way
+    starts: List[List[int]] = [[] for _ in range(n_lines)]
+    for r in range(n_requests):
+        rid = "%016x" % rng.getrandbits(64)
+        while rid in ids or rid.isalpha():          # (an id holds a digit)
+            rid = "%016x" % rng.getrandbits(64)
+        ids.add(rid)
+        a = rng.randrange(max(1, n_lines - 1))
+        b = min(n_lines - 1, a + rng.randint(1, span))
+        fails = rng.random() < fail_rate and a < b and a not in forced and b not in forced
+        if fails:
+            forced[a] = forced[b] = r
+        reqs.append((rid, a, b, fails))
+        starts[a].append(r)
+    failing: Dict[str, List[int]] = {rid: [] for rid, _, _, fails in reqs if fails}
+    active: List[int] = []
+    out = []
+    for i, line in enumerate(lines):
+        active += starts[i]
+        active = [r for r in active if reqs[r][2] >= i]
+        r = forced.get(i, rng.choice(active) if active else None)
+        if r is not None:
+            rid, _, b, fails = reqs[r]
+            if fails and i == b:
+                line = "2025-09-19T12:%02d:%02d.%03dZ ERROR [gateway] %s" % ((i // 60) % 60, i % 60, i % 1000,
+                                                                            CORRELATED_FAIL)
+            line += " rid=" + rid
+            if fails:
+                failing[rid].append(i)
+        out.append(line)
+        out.append("\r\n" if rng.random() < crlf_rate else "\n")
+    return "".join(out), failing
 
 
 def trace_sites(n: int, seed: int = 0) -> List[Tuple[str, List[str]]]:
