@@ -1229,6 +1229,26 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sel"), py::arg("n"),
         py::arg("tab"), py::arg("min_len"), py::arg("out_line"), py::arg("out_key"), py::arg("hit"), py::arg("cap"),
         py::arg("cnt"), py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  // ---- values report (values.hip): template signature and numeric fields of every line
+  m.def("line_vals", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, uint64_t sig,
+                        uint64_t out_line, uint64_t out_key, uint64_t out_val, int64_t cap, uint64_t cnt, uint64_t s,
+                        bool dev, int per_block) {
+    ValLinesArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.nl = nl;
+    A.sig = P<int64_t>(sig);
+    A.out_line = P<int32_t>(out_line); A.out_key = P<int64_t>(out_key); A.out_val = P<int32_t>(out_val);
+    A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      line_vals_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    line_vals_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sig"),
+        py::arg("out_line"), py::arg("out_key"), py::arg("out_val"), py::arg("cap"), py::arg("cnt"),
+        py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

@@ -499,6 +499,29 @@ void line_keys_dev(const KeyLinesArgs& A, uint64_t stream, int per_block = 0);
 void line_keys_host(const KeyLinesArgs& A);
 }  // namespace lp
 
+// ---- values report (values.hip): template signature and numeric fields of every line
+namespace lp {
+struct ValLinesArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t nl;                // lines of ls / ll, at most 2^31 - 1: every one is walked
+  // outputs: sig[i] = template signature of line i (gaps_core.h); the values of every line (of its
+  // first 8 fields, val_core.h) as (line number, val_key(signature, field), value) triples, the
+  // first `cap` of them; cnt[0] += triples (all of them: above cap the caller re-runs, as with
+  // line_keys_dev), cnt[1] += lines with at least one value
+  int64_t* sig;
+  int32_t* out_line; int64_t* out_key; int32_t* out_val;
+  int64_t cap;
+  unsigned long long* cnt;   // [2], zeroed by the caller
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from nl.
+// GPU: the triples come in no particular order
+void line_vals_dev(const ValLinesArgs& A, uint64_t stream, int per_block = 0);
+// appends in line order, the fields of a line in byte order
+void line_vals_host(const ValLinesArgs& A);
+}  // namespace lp
+
 // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
 namespace lp {
 // out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN

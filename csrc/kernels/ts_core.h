@@ -60,7 +60,10 @@ struct TsBytes {
       cur_off = off;
     }
     const int j = (int)(a & 15);
-    const uint32_t w = (j < 4) ? cur.x : (j < 8) ? cur.y : (j < 12) ? cur.z : cur.w;
+    // (the four words are read first and the selects choose among values: a select among the
+    // members themselves can become one load at a computed address, which puts `cur` into scratch)
+    const uint32_t x0 = cur.x, x1 = cur.y, x2 = cur.z, x3 = cur.w;
+    const uint32_t w = (j < 4) ? x0 : (j < 8) ? x1 : (j < 12) ? x2 : x3;
     return (int)((w >> (8 * (j & 3))) & 0xFFu);
 #else
     return text[start + t];
@@ -89,8 +92,10 @@ LP_HD uint32_t ts_core_mask(int c) {
 // The low four bits of the last TS_CORE bytes ride along in two words, so the digits of the match
 // are at hand when it completes and no byte is read twice: the walk only moves forward.
 // Fraction and zone follow greedily, without backtracking; the fields are validated last, and a
-// leftmost match with an invalid field means no stamp.
-LP_HD int64_t line_ts_at(const uint8_t* __restrict__ text, int64_t tbytes, int64_t start, int n) {
+// leftmost match with an invalid field means no stamp. `end`: the offset in the line of the first
+// byte behind the stamp -- behind its zone, where it has one -- or 0 without a valid stamp.
+LP_HD int64_t ts_scan_at(const uint8_t* __restrict__ text, int64_t tbytes, int64_t start, int n, int& end) {
+  end = 0;
   if (start < 0) start = 0;
   if (start > tbytes) start = tbytes;
   if (n > TS_MAX_BYTES) n = TS_MAX_BYTES;
@@ -135,8 +140,10 @@ LP_HD int64_t line_ts_at(const uint8_t* __restrict__ text, int64_t tbytes, int64
   }
   int zone = 0;                           // minutes east of UTC
   bool zone_ok = true;
+  int qe = q;                             // the end of the match, zone included
   {
     const int c = B.at(q);
+    if (c == 'Z') qe = q + 1;
     if (c == '+' || c == '-') {
       int r = q + 3;
       if (ts_digit(B.at(q + 1)) && ts_digit(B.at(q + 2))) {
@@ -146,6 +153,7 @@ LP_HD int64_t line_ts_at(const uint8_t* __restrict__ text, int64_t tbytes, int64
           const int zm = (B.at(r) - '0') * 10 + (B.at(r + 1) - '0');
           zone_ok = zh <= 23 && zm <= 59;
           zone = (c == '-' ? -1 : 1) * (zh * 60 + zm);
+          qe = r + 2;
         }
       }
     }
@@ -153,7 +161,22 @@ LP_HD int64_t line_ts_at(const uint8_t* __restrict__ text, int64_t tbytes, int64
   if (!zone_ok || y < 1970 || mo < 1 || mo > 12 || d < 1 || d > ts_days_in_month(y, mo) || h > 23 || mi > 59 || s > 59)
     return TS_NONE;
   const int64_t secs = ts_days_from_civil(y, mo, d) * 86400 + h * 3600 + mi * 60 + s - (int64_t)zone * 60;
+  end = qe;
   return secs * 1000 + frac;
+}
+
+LP_HD int64_t line_ts_at(const uint8_t* __restrict__ text, int64_t tbytes, int64_t start, int n) {
+  int end;
+  return ts_scan_at(text, tbytes, start, n, end);
+}
+
+// the stamp end of the line: the offset of the first byte behind its valid stamp (the end of the
+// grammar's match: fraction and zone included), or 0 where line_ts_at gives TS_NONE -- an invalid
+// stamp hides nothing (values.hip). At most TS_MAX_BYTES bytes of the line are read.
+LP_HD int line_ts_span_at(const uint8_t* __restrict__ text, int64_t tbytes, int64_t start, int n) {
+  int end;
+  ts_scan_at(text, tbytes, start, n, end);
+  return end;
 }
 
 }  // namespace lp

@@ -36,6 +36,11 @@
                                                the ids on the event lines of a log (request ids,
                                                trace ids, pod hashes, addresses) followed through
                                                the log: which other lines hold them (JSON)
+  values    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--top N]
+            [--order peak|max|count|first] [--min-count N] [--min-fill F] [--all-fields]
+                                               the numeric fields of the line templates of a log:
+                                               count, sum, min, max, and the line of the largest
+                                               value -- the fields that peak first (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -197,6 +202,22 @@ def cmd_correlate(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_values(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    kw = {"top": args.top, "order": args.order, "min_count": args.min_count, "min_fill": args.min_fill,
+          "varying": not args.all_fields}
+    try:
+        if args.stream:
+            rep = lp.values_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.values_file(args.file, **kw)
+    except ValueError as e:                 # a count or a share out of range, a log of 2^32 lines
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -277,12 +298,27 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="list only the ids on at least N lines (default 2)")
     c.add_argument("--max-share", type=float, default=0.25, metavar="F",
                    help="drop the ids on more than this share of all lines (default 0.25)")
+    v = sub.add_parser("values", help="the numeric fields of the line templates of a log file and their peaks")
+    v.add_argument("file")
+    _library_options(v)
+    v.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    v.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    v.add_argument("--top", type=int, default=20, help="fields reported (default 20)")
+    v.add_argument("--order", choices=("peak", "max", "count", "first"), default="peak",
+                   help="largest value in units of the mean first (default), largest value first, most values "
+                        "first, or in order of first appearance")
+    v.add_argument("--min-count", type=int, default=5, metavar="N",
+                   help="list only the fields with at least N values (default 5)")
+    v.add_argument("--min-fill", type=float, default=0.9, metavar="F",
+                   help="list only the fields with a value on at least this share of their template's lines "
+                        "(default 0.9)")
+    v.add_argument("--all-fields", action="store_true", help="list the fields whose value never changes too")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
-            "leadup": cmd_leadup, "correlate": cmd_correlate}[args.cmd](args, cfg)
+            "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

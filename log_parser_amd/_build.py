@@ -40,6 +40,7 @@ SOURCES = [
     ("kernels/novelty.hip", "hip"),
     ("kernels/leadup.hip", "hip"),
     ("kernels/correlate.hip", "hip"),
+    ("kernels/values.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),

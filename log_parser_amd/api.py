@@ -36,6 +36,10 @@ to embedders, with what an in-process user needs beyond one call at a time:
   the event lines of a log, followed through the whole log -- ``golden.correlate``;
   ``correlate_stream`` / ``correlate_resident`` for one log too large for one piece (the source
   is walked twice);
+* ``values`` / ``values_file``: the numeric fields of the line templates of a log -- count, sum,
+  min, max and where the largest value is -- ``golden.values``; ``values_stream`` /
+  ``values_resident`` for one log too large for one piece, ``value_accumulator`` for a log that
+  arrives over time;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -422,6 +426,67 @@ class LogParser:
         acc = self.leadup_accumulator(window)
         acc.add_resident(resident)
         return acc.report(top, order, min_count)
+
+    # ---- values report -----------------------------------------------------------------------
+    def values(self, logs, top: Optional[int] = 20, order: str = "peak", min_count: int = 5, min_fill: float = 0.9,
+               varying: bool = True) -> dict:
+        """Which numbers do the line templates of one document (str or bytes) carry, and where do
+        they peak? The digit-holding tokens of a line behind its stamp are its *fields*, numbered
+        in byte order (the first 8 count); a field has a value where its token is up to nine digits
+        and up to three unit letters (``12``, ``31874ms``, ``512MB``). Per template and field:
+        ``count``, ``sum``, ``min``, ``max``, ``mean``, ``peak`` = max / mean, ``maxLine`` (the
+        first line that holds the max), first and last line with their values, ``lines`` (all
+        lines of the template), ``fill`` = count / lines, and the first line as the example.
+        Listed are the fields with ``count >= min_count`` and ``count >= min_fill * lines`` (a hex
+        or id field only now and then looks like a number) and, with ``varying``, ``min < max``.
+        ``order="peak"``: the largest value in units of the mean first; ``"max"``: largest value
+        first; ``"count"``: most values first; ``"first"``: in order of first appearance;
+        ``top=None``: every field. No pattern takes part. ``Engine.values_bytes``;
+        ``golden.values`` is the specification; the frequency window is not touched."""
+        from .values import check_args
+        check_args(order, min_count, min_fill)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("values"):
+            return self.engine.values_bytes(logs, top=top, order=order, min_count=min_count, min_fill=min_fill,
+                                            varying=varying)
+
+    def values_file(self, path: str, top: Optional[int] = 20, order: str = "peak", min_count: int = 5,
+                    min_fill: float = 0.9, varying: bool = True) -> dict:
+        """``values`` of a log file, read as ONE document whatever its size."""
+        from .values import check_args
+        check_args(order, min_count, min_fill)
+        with open(path, "rb") as f:
+            return self.values(f.read(), top=top, order=order, min_count=min_count, min_fill=min_fill, varying=varying)
+
+    def value_accumulator(self, line_base: int = 0):
+        """A ``values.ValueAccumulator`` on this parser's engine for a log that arrives over time
+        (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then ``report``);
+        each of its calls runs under the batcher guard and the lock of ``values``."""
+        from .values import ValueAccumulator
+        with self._engine_guard("values"):
+            return ValueAccumulator(self.engine, guard=lambda: self._engine_guard("values"), line_base=line_base)
+
+    def values_stream(self, src_or_path, chunk_bytes: Optional[int] = None, top: Optional[int] = 20,
+                      order: str = "peak", min_count: int = 5, min_fill: float = 0.9, varying: bool = True) -> dict:
+        """``values`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). A field belongs to
+        one line, so the report is exactly the one-document report, whatever the chunk size."""
+        from .values import check_args
+        check_args(order, min_count, min_fill)
+        acc = self.value_accumulator()
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(top, order, min_count, min_fill, varying)
+
+    def values_resident(self, resident, top: Optional[int] = 20, order: str = "peak", min_count: int = 5,
+                        min_fill: float = 0.9, varying: bool = True) -> dict:
+        """``values`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        from .values import check_args
+        check_args(order, min_count, min_fill)
+        acc = self.value_accumulator()
+        acc.add_resident(resident)
+        return acc.report(top, order, min_count, min_fill, varying)
 
     # ---- correlation report ------------------------------------------------------------------
     def correlate(self, logs, min_len: int = 8, top: Optional[int] = 20, order: str = "events", min_lines: int = 2,

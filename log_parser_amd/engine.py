@@ -894,6 +894,15 @@ class Engine:
         from .correlate import correlate_document
         return correlate_document(self, text, n, data, min_len, top, order, min_lines, max_share)
 
+    # ------------------------------------------------------------------ values report
+    def values_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "peak", min_count: int = 5,
+                     min_fill: float = 0.9, varying: bool = True) -> dict:
+        """Which numbers do the line templates of one document carry, and where do they peak?
+        (values.py; ``golden.values`` is the specification.) The matchers do not run, nothing is
+        scored and the frequency window is not touched."""
+        from .values import values_document
+        return values_document(self, bytes(data), top, order, min_count, min_fill, varying)
+
     # ------------------------------------------------------------------ trace report
     def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
                      unexplained_only: bool = False) -> dict:

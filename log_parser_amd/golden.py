@@ -27,6 +27,7 @@ import time
 import uuid
 from collections import deque
 from datetime import datetime, timedelta, timezone
+from fractions import Fraction
 from typing import Callable, Dict, List, Optional, Sequence
 
 from .models.schema import Pattern, PatternSet, pattern_to_json
@@ -780,6 +781,152 @@ def timeline(logs, pattern_sets: List[PatternSet], params: ScoringParams, bucket
         out["lastEvent"] = ref
     out["buckets"] = [{"start": iso_ms(t), **buckets[t]} for t in sorted(buckets)]
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Values report (an extra, as the gap report): every other report throws the numbers of a line
+# away -- ``line_template`` turns each digit-holding token into ``0``. This one keeps them: per
+# template and field, how many values, their sum, smallest and largest, where the largest is, so
+# that the ``served in 31874ms`` among ten thousand ``served in 12ms`` comes first. These functions
+# are the specification of ``log_parser_amd/values.py`` and of the value kernel
+# (csrc/kernels/val_core.h, values.hip).
+#
+# Known limits: no signs; a decimal (``12.5``) is two fields; only the stamps of ``line_timestamp``
+# are skipped; the unit is ignored, so ``2s`` and ``15ms`` in one field mix; a hex value without a
+# digit behind its ``x`` (``0xff``) reads as 0 on that line; two (template, field) pairs may share
+# a 64-bit key; only the first ``SIG_MAX_BYTES`` bytes of a line and its first ``VAL_PER_LINE``
+# fields count.
+
+VAL_PER_LINE = 8
+VAL_MAX_LINES = 1 << 32         # a log has fewer lines than this (the packed ordinals of values.py)
+_VALUE = re.compile(rb"([0-9]{1,9})[A-Za-z]{0,3}")
+
+
+def stamp_end(line: bytes) -> int:
+    """The end of the ``_STAMP`` match where ``line_timestamp(line)`` is not None, else 0: an
+    invalid stamp hides nothing."""
+    line = bytes(line)
+    return 0 if line_timestamp(line) is None else _STAMP.search(line).end()
+
+
+def line_fields(line: bytes) -> List[tuple]:
+    """[(j, value or None, token)]: the *fields* of a line are the digit-holding tokens (maximal
+    ``[0-9A-Za-z]`` runs, as in ``line_template``) of its first ``SIG_MAX_BYTES`` bytes (a token
+    still open there ends there) that START at byte ``stamp_end(line)`` or later, in byte order,
+    numbered j = 0, 1, ...; only the first ``VAL_PER_LINE`` count. A field has a value iff its
+    token is ``[0-9]{1,9}[A-Za-z]{0,3}`` from start to end: the integer of the digit prefix."""
+    line = bytes(line)
+    q = stamp_end(line)
+    out = []
+    for m in _TOKEN.finditer(line[:SIG_MAX_BYTES]):
+        t = m.group()
+        if m.start() < q or not _DIGIT.search(t):
+            continue
+        if len(out) == VAL_PER_LINE:
+            break
+        v = _VALUE.fullmatch(t)
+        out.append((len(out), int(v.group(1)) if v else None, t))
+    return out
+
+
+def line_values(line: bytes) -> List[tuple]:
+    """[(j, value)] of the fields of a line (``line_fields``) that have a value."""
+    return [(j, v) for j, v, _ in line_fields(line) if v is not None]
+
+
+def val_key(sig: int, j: int) -> int:
+    """The 64-bit group key of field ``j`` of the template with signature ``sig``."""
+    return ((sig ^ (j + 1)) * _FNV_PRIME) & 0xFFFFFFFFFFFFFFFF
+
+
+def values_check_args(order: str = "peak", min_count: int = 5, min_fill: float = 0.9) -> None:
+    if order not in ("peak", "max", "count", "first"):
+        raise ValueError("order must be 'peak', 'max', 'count' or 'first'")
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+        raise ValueError("min_count must be an integer >= 1")
+    if isinstance(min_fill, bool) or not isinstance(min_fill, (int, float)) or not 0.0 <= min_fill <= 1.0:
+        raise ValueError("min_fill must be in [0, 1]")
+
+
+def values_order_key(order: str, sig: int, j: int, count: int, total: int, vmax: int, first: int):
+    """The sort key of a group: exact arithmetic (ints and ``Fraction``), ``sig`` unsigned."""
+    if order == "peak":
+        return ((0, -Fraction(vmax * count, total)) if total else (1, 0), -vmax, first, sig, j)
+    if order == "max":
+        return (-vmax, first, sig, j)
+    if order == "count":
+        return (-count, first, sig, j)
+    return (first, j)
+
+
+def values_row(sig: int, j: int, count: int, total: int, vmin: int, vmax: int, max_line: int, first: int,
+               first_value: int, last: int, last_value: int, lines: int, raw: bytes) -> dict:
+    """One row of the report from its numbers (lines 0-based) and the first line with a value of
+    the group: ValueError unless that line has the template ``sig`` and holds ``first_value`` in
+    field ``j``."""
+    if line_signature(raw) != sig or (j, first_value) not in line_values(raw):
+        raise ValueError("values: line %d does not hold field %d of %016x with the value %d"
+                         % (first + 1, j, sig, first_value))
+    return {"signature": "%016x" % sig, "field": j, "token": line_fields(raw)[j][2].decode("ascii"),
+            "count": count, "lines": lines, "fill": count / lines, "sum": total, "min": vmin, "max": vmax,
+            "mean": total / count, "peak": (vmax * count / total) if total else 0.0,
+            "maxLine": max_line + 1, "firstLine": first + 1, "first": first_value,
+            "lastLine": last + 1, "last": last_value,
+            "template": line_template(raw).decode("utf-8", errors="replace"),
+            "example": raw.decode("utf-8", errors="replace")}
+
+
+def values(logs, top: Optional[int] = 20, order: str = "peak", min_count: int = 5, min_fill: float = 0.9,
+           varying: bool = True) -> dict:
+    """The values report of ``logs`` (str or bytes; no pattern takes part). A *group* is (template
+    signature of the line, field number j). Per group: ``count`` values, their exact ``sum``,
+    ``min``, ``max``, ``maxLine`` (the first line that holds the max), ``firstLine`` / ``first``
+    and ``lastLine`` / ``last`` (the first / last line with a value, and that value), ``lines``
+    (all lines of the template), ``fill`` = count / lines, ``mean``, ``peak`` = max * count / sum
+    (the largest value in units of the mean; 0.0 when the sum is 0), the field's ``token`` on the
+    first line and that line as the ``example``. Dropped are the groups with ``count <
+    min_count``, those with ``count < min_fill * lines`` (a hex or id field that only now and then
+    looks like a number) and, with ``varying``, those with ``min == max``. ``order="peak"``: by
+    (-peak, -max, first line, signature, field), a zero sum last; ``"max"``: (-max, first line,
+    signature, field); ``"count"``: (-count, ...); ``"first"``: (first line, field). ``values``
+    counts all values, ``valueLines`` the lines with at least one, ``templates`` the templates of
+    all lines, ``fields`` the groups before the filters."""
+    values_check_args(order, min_count, min_fill)
+    raws = [line.encode("utf-8", errors="surrogateescape") for line in split_lines(_as_text(logs))]
+    if len(raws) >= VAL_MAX_LINES:
+        raise ValueError("values: a log of 2^32 lines or more")
+    per_sig: Dict[int, int] = {}
+    groups: Dict[tuple, dict] = {}
+    n_values = value_lines = 0
+    for i, raw in enumerate(raws):
+        sig = line_signature(raw)
+        per_sig[sig] = per_sig.get(sig, 0) + 1
+        vals = line_values(raw)
+        n_values += len(vals)
+        value_lines += bool(vals)
+        for j, v in vals:
+            g = groups.get((sig, j))
+            if g is None:
+                g = groups[(sig, j)] = {"count": 0, "sum": 0, "min": v, "max": v, "maxLine": i, "first": i,
+                                        "firstValue": v}
+            g["count"] += 1
+            g["sum"] += v
+            g["min"] = min(g["min"], v)
+            if v > g["max"]:
+                g["max"], g["maxLine"] = v, i
+            g["last"], g["lastValue"] = i, v
+    listed = [kv for kv in groups.items()
+              if kv[1]["count"] >= min_count and kv[1]["count"] >= min_fill * per_sig[kv[0][0]]
+              and (not varying or kv[1]["min"] < kv[1]["max"])]
+    listed.sort(key=lambda kv: values_order_key(order, kv[0][0], kv[0][1], kv[1]["count"], kv[1]["sum"], kv[1]["max"],
+                                                kv[1]["first"]))
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    return {"totalLines": len(raws), "valueLines": value_lines, "values": n_values, "templates": len(per_sig),
+            "fields": len(groups),
+            "top": [values_row(sig, j, g["count"], g["sum"], g["min"], g["max"], g["maxLine"], g["first"],
+                               g["firstValue"], g["last"], g["lastValue"], per_sig[sig], raws[g["first"]])
+                    for (sig, j), g in listed]}
 
 
 # ---------------------------------------------------------------------------------------------

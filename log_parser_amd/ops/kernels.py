@@ -1199,6 +1199,44 @@ def line_keys(text, line_start, line_len, sel: Optional[torch.Tensor] = None, ta
 
 
 # ---------------------------------------------------------------------------------------------
+# values report (csrc/kernels/values.hip): template signature and numeric fields of every line
+
+VL_MAX_LINES = 2048         # lines per block of k_line_vals at most
+VAL_PER_LINE = 8            # fields of a line that count (csrc/kernels/val_core.h)
+
+
+def line_values(text, line_start, line_len, cap: Optional[int] = None, per_block: int = 0):
+    """Template signature and values (``golden.line_values``) of every line: (sig int64[L], line
+    int32[n], key int64[n], value int32[n], (n, lines with at least one value)) -- a value of
+    field j of line i is the triple (i, ``golden.val_key(sig[i], j)``, value). One pass over the
+    text (k_line_vals) with the capacity protocol of ``line_keys``. ``per_block``: lines per block
+    instead of the size the launch picks (tests). GPU: the triples come in no particular order;
+    CPU: in line order, the fields of a line in byte order."""
+    dev = text.device
+    L = line_start.numel()
+    if per_block and not 0 < per_block <= VL_MAX_LINES:
+        raise ValueError("line_values: per_block must be 1..%d" % VL_MAX_LINES)
+    sig = torch.empty(L, dtype=torch.int64, device=dev)
+    if L == 0:
+        return (sig, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev), (0, 0))
+    # a re-run costs a whole pass over the text, a triple 16 bytes: a log line holds a number or two
+    cap = max(1024, 2 * L) if cap is None else max(0, int(cap))
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_key = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        out_val = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        N.line_vals(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, sig.data_ptr(),
+                    out_line.data_ptr(), out_key.data_ptr(), out_val.data_ptr(), cap, cnt.data_ptr(), _s(text),
+                    text.is_cuda, per_block)
+        m, lines = cnt.tolist()
+        if m <= cap:
+            return sig, out_line[:m], out_key[:m], out_val[:m], (m, lines)
+        cap = m
+
+
+# ---------------------------------------------------------------------------------------------
 # log timeline (csrc/kernels/timeline.hip): the timestamp of every line, counts per time bucket
 
 TS_NONE = -(1 << 63)        # a line without a stamp / without an effective time (csrc/kernels/ts_core.h)

@@ -388,6 +388,31 @@ def templated_log(n_lines: int, templates: List[str], seed: int = 0, crlf_rate: 
     return "".join(parts)
 
 
+METRIC_TEMPLATE = "2025-09-19T12:%02d:%02d.%03dZ INFO  [gateway] served request in %dms"
+
+
+def metric_log(n_lines: int, templates: List[str], seed: int = 0, burst_at: float = 0.8,
+               burst_lines: int = 20) -> Tuple[str, List[int]]:
+    """A ``templated_log`` with one extra template, ``INFO  [gateway] served request in %dms``, on
+    about a tenth of its lines. Its value is uniform in 5..50, except on ``burst_lines``
+    consecutive occurrences of the template from line ``burst_at * n_lines`` on, where it is
+    uniform in 30000..60000: a latency peak that every report which drops the numbers cannot
+    see. Returns (text, the lines of the burst, 0-based and ascending) -- known by construction."""
+    rng = random.Random(seed)
+    lines = templated_log(n_lines, templates, seed=seed).split("\n")[:n_lines]
+    start = int(burst_at * n_lines)
+    burst: List[int] = []
+    for i in range(n_lines):
+        if rng.random() >= 0.1:
+            continue
+        slow = i >= start and len(burst) < burst_lines
+        if slow:
+            burst.append(i)
+        ms = rng.randint(30000, 60000) if slow else rng.randint(5, 50)
+        lines[i] = METRIC_TEMPLATE % ((i // 60) % 60, i % 60, i % 1000, ms)
+    return "".join(line + "\n" for line in lines), burst
+
+
 CORRELATED_FAIL = "request aborted: upstream deadline exceeded"     # what the last line of a failing request says
 
 
