@@ -96,6 +96,29 @@ static GapRows gr_from(const py::tuple& t) {
   return R;
 }
 
+// (key, sig, bucket, count, first, used, cap) of a cell table (cell_table.h)
+static CellTab ct_from(const py::tuple& t) {
+  CellTab T;
+  T.key = P<int64_t>(t[0].cast<uint64_t>());
+  T.sig = P<int64_t>(t[1].cast<uint64_t>());
+  T.bucket = P<int64_t>(t[2].cast<uint64_t>());
+  T.count = P<unsigned long long>(t[3].cast<uint64_t>());
+  T.first = P<long long>(t[4].cast<uint64_t>());
+  T.used = P<unsigned long long>(t[5].cast<uint64_t>());
+  T.cap = t[6].cast<int64_t>();
+  return T;
+}
+
+// (sig, bucket, count, first) row columns
+static CellRows cr_from(const py::tuple& t) {
+  CellRows R;
+  R.sig = P<int64_t>(t[0].cast<uint64_t>());
+  R.bucket = P<int64_t>(t[1].cast<uint64_t>());
+  R.count = P<int64_t>(t[2].cast<uint64_t>());
+  R.first = P<int64_t>(t[3].cast<uint64_t>());
+  return R;
+}
+
 static ScoreTables st_from(const py::tuple& t) {
   ScoreTables T;
   int i = 0;
@@ -1249,6 +1272,52 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sig"),
         py::arg("out_line"), py::arg("out_key"), py::arg("out_val"), py::arg("cap"), py::arg("cnt"),
         py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  // ---- trends report (trends.hip): stamp and signature of every line, the cell table
+  m.def("line_stamps", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, uint64_t sig, uint64_t ts,
+                          uint64_t s, bool dev, int per_block) {
+    LineStampsArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.nl = nl;
+    A.sig = P<int64_t>(sig); A.ts = P<int64_t>(ts);
+    if (dev) {
+      line_stamps_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    line_stamps_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sig"), py::arg("ts"),
+        py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  m.def("cell_fold", [](py::tuple tab, uint64_t sig, uint64_t eff, int64_t n, int64_t line_base, int64_t W, uint64_t s,
+                        bool dev, int tile) {
+    const CellTab T = ct_from(tab);
+    if (dev) {
+      cell_fold_dev(T, P<const int64_t>(sig), P<const int64_t>(eff), n, line_base, W, s, tile);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    cell_fold_host(T, P<const int64_t>(sig), P<const int64_t>(eff), n, line_base, W); },
+        py::arg("tab"), py::arg("sig"), py::arg("eff"), py::arg("n"), py::arg("line_base"), py::arg("W"),
+        py::arg("stream"), py::arg("dev"), py::arg("tile") = 0);
+  m.def("cell_rows", [](py::tuple tab, py::tuple rows, int64_t out_cap, uint64_t cnt, uint64_t s, bool dev) {
+    const CellTab T = ct_from(tab);
+    const CellRows R = cr_from(rows);
+    if (dev) {
+      cell_rows_dev(T, R, out_cap, P<unsigned long long>(cnt), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    cell_rows_host(T, R, out_cap, P<unsigned long long>(cnt)); },
+        py::arg("tab"), py::arg("rows"), py::arg("out_cap"), py::arg("cnt"), py::arg("stream"), py::arg("dev"));
+  m.def("cell_reinsert", [](py::tuple tab, py::tuple rows, int64_t n, uint64_t s, bool dev) {
+    const CellTab T = ct_from(tab);
+    const CellRows R = cr_from(rows);
+    if (dev) {
+      cell_reinsert_dev(T, R, n, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    cell_reinsert_host(T, R, n); },
+        py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

@@ -555,6 +555,40 @@ void tl_hist_dev(const TlHistArgs& A, uint64_t stream);
 void tl_hist_host(const TlHistArgs& A);
 }  // namespace lp
 
+// ---- trends report (trends.hip): stamp and signature of every line, counts per (signature, time bucket)
+#include "cell_table.h"
+namespace lp {
+struct LineStampsArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t nl;                // lines of ls / ll, at most 2^31 - 1: every one is walked
+  // outputs: sig[i] = template signature of line i (gaps_core.h), ts[i] = epoch milliseconds of its
+  // stamp or TS_NONE (ts_core.h)
+  int64_t* sig; int64_t* ts;
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from nl
+void line_stamps_dev(const LineStampsArgs& A, uint64_t stream, int per_block = 0);
+void line_stamps_host(const LineStampsArgs& A);
+struct CellRows {            // rows of a cell table, or the rows to put into one
+  int64_t* sig; int64_t* bucket; int64_t* count; int64_t* first;
+};
+// n consecutive lines, line i with the signature sig[i], the effective time eff[i] (TS_NONE: undated,
+// the cell of the bucket CT_UNDATED) and the global number line_base + i, into the table: per cell
+// (sig, floor(eff / W)) the number of lines and the smallest line. The caller keeps
+// 2 * (used + n) <= cap. tile: lines per block (256..2048, a multiple of 256), 0: chosen from n
+void cell_fold_dev(const CellTab& T, const int64_t* sig, const int64_t* eff, int64_t n, int64_t line_base, int64_t W,
+                   uint64_t stream, int tile = 0);
+// the occupied slots as rows, in no particular order: the first out_cap of them; *cnt += all of them
+void cell_rows_dev(const CellTab& T, const CellRows& R, int64_t out_cap, unsigned long long* cnt, uint64_t stream);
+// n rows of distinct cells into a table that holds none of them (growth); used[0] is left to the
+// caller, who knows it is n
+void cell_reinsert_dev(const CellTab& T, const CellRows& R, int64_t n, uint64_t stream);
+void cell_fold_host(const CellTab& T, const int64_t* sig, const int64_t* eff, int64_t n, int64_t line_base, int64_t W);
+void cell_rows_host(const CellTab& T, const CellRows& R, int64_t out_cap, unsigned long long* cnt);
+void cell_reinsert_host(const CellTab& T, const CellRows& R, int64_t n);
+}  // namespace lp
+
 // ---- trace report (traces.hip): stack traces as runs of frame / cause lines, one row per trace
 #include "trace_core.h"
 namespace lp {

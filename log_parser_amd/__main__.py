@@ -41,6 +41,12 @@
                                                the numeric fields of the line templates of a log:
                                                count, sum, min, max, and the line of the largest
                                                value -- the fields that peak first (JSON)
+  trends    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--bucket S]
+            [--at T|first-event|first-error] [--ratio R] [--min-count N] [--kind K] [--order O]
+            [--top N]
+                                               the line templates of a log that started, stopped,
+                                               surged or faded across a pivot in the log's own
+                                               time: what changed (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -218,6 +224,23 @@ def cmd_values(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_trends(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    at = int(args.at) if args.at is not None and args.at.lstrip("-").isdigit() else args.at
+    kw = {"bucket_seconds": args.bucket, "at": at, "ratio": args.ratio, "min_count": args.min_count, "kind": args.kind,
+          "order": args.order, "top": args.top}
+    try:
+        if args.stream:
+            rep = lp.trends_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.trends_file(args.file, **kw)
+    except ValueError as e:                 # a pivot outside the log's span, a span against max_buckets
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -313,12 +336,32 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="list only the fields with a value on at least this share of their template's lines "
                         "(default 0.9)")
     v.add_argument("--all-fields", action="store_true", help="list the fields whose value never changes too")
+    d = sub.add_parser("trends", help="line templates of a log file that started, stopped, surged or faded over its time")
+    d.add_argument("file")
+    _library_options(d)
+    d.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    d.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    d.add_argument("--bucket", type=int, default=60, metavar="SECONDS", help="bucket width (default 60)")
+    d.add_argument("--at", default=None, metavar="T",
+                   help="the pivot: epoch milliseconds, a timestamp, first-event or first-error (default: the middle "
+                        "of the log's span)")
+    d.add_argument("--ratio", type=int, default=4, metavar="R",
+                   help="the factor by which a rate must change to count as surged or faded (default 4)")
+    d.add_argument("--min-count", type=int, default=5, metavar="N",
+                   help="list only the templates with at least N dated lines (default 5)")
+    d.add_argument("--kind", choices=("started", "stopped", "surged", "faded", "steady", "all"), default=None,
+                   help="list only this kind (default: all but steady)")
+    d.add_argument("--order", choices=("change", "count", "first"), default="change",
+                   help="largest change of rate first (default), most dated lines first, or in order of first "
+                        "appearance")
+    d.add_argument("--top", type=int, default=20, help="templates reported (default 20)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
-            "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values}[args.cmd](args, cfg)
+            "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values,
+            "trends": cmd_trends}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

@@ -42,6 +42,7 @@ SOURCES = [
     ("kernels/correlate.hip", "hip"),
     ("kernels/values.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
+    ("kernels/trends.hip", "hip"),
     ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),

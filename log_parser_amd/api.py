@@ -40,6 +40,10 @@ to embedders, with what an in-process user needs beyond one call at a time:
   min, max and where the largest value is -- ``golden.values``; ``values_stream`` /
   ``values_resident`` for one log too large for one piece, ``value_accumulator`` for a log that
   arrives over time;
+* ``trends`` / ``trends_file``: the line templates of a log that started, stopped, surged or
+  faded across a pivot in its own time -- ``golden.trends``; ``trends_stream`` /
+  ``trends_resident`` for one log too large for one piece, ``trend_accumulator`` for a log that
+  arrives over time;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -487,6 +491,73 @@ class LogParser:
         acc = self.value_accumulator()
         acc.add_resident(resident)
         return acc.report(top, order, min_count, min_fill, varying)
+
+    # ---- trends report -----------------------------------------------------------------------
+    def trends(self, logs, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
+               kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,
+               max_buckets: int = 65536) -> dict:
+        """What changed over the time of one document (str or bytes)? Lines are counted per
+        template and time bucket of ``bucket_seconds`` (a line without a stamp takes the time of
+        the nearest earlier stamped line); a pivot bucket splits the span of the log: the middle
+        (``at=None``), the bucket of ``at`` (epoch milliseconds or a timestamp), or that of the
+        timeline's ``"first-event"`` / ``"first-error"``. A template with no dated line before the
+        pivot ``started``, with none from it on ``stopped``; one whose rate per bucket rose or fell
+        by the factor ``ratio`` (an integer >= 2) ``surged`` or ``faded``; the others are
+        ``steady``. Listed are the templates with ``datedLines >= min_count`` of the kind ``kind``
+        (None: all but steady; ``"all"``), ``order="change"``: largest change of rate first;
+        ``"count"``: most dated lines first; ``"first"``: in order of first appearance;
+        ``top=None``: every template. No pattern and no baseline takes part, except for the two
+        named pivots. ``Engine.trends_bytes``; ``golden.trends`` is the specification; the
+        frequency window is not touched."""
+        from .trends import check_args
+        check_args(bucket_seconds, at, ratio, min_count, kind, order, max_buckets)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("trends"):
+            return self.engine.trends_bytes(logs, bucket_seconds=bucket_seconds, at=at, ratio=ratio, min_count=min_count,
+                                            kind=kind, order=order, top=top, max_buckets=max_buckets)
+
+    def trends_file(self, path: str, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
+                    kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,
+                    max_buckets: int = 65536) -> dict:
+        """``trends`` of a log file, read as ONE document whatever its size."""
+        from .trends import check_args
+        check_args(bucket_seconds, at, ratio, min_count, kind, order, max_buckets)
+        with open(path, "rb") as f:
+            return self.trends(f.read(), bucket_seconds=bucket_seconds, at=at, ratio=ratio, min_count=min_count,
+                               kind=kind, order=order, top=top, max_buckets=max_buckets)
+
+    def trend_accumulator(self, bucket_seconds: int = 60):
+        """A ``trends.TrendAccumulator`` on this parser's engine for a log that arrives over time
+        (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then ``report``);
+        each of its calls runs under the batcher guard and the lock of ``trends``."""
+        from .trends import TrendAccumulator
+        with self._engine_guard("trends"):
+            return TrendAccumulator(self.engine, bucket_seconds, guard=lambda: self._engine_guard("trends"))
+
+    def trends_stream(self, src_or_path, chunk_bytes: Optional[int] = None, bucket_seconds: int = 60, at=None,
+                      ratio: int = 4, min_count: int = 5, kind: Optional[str] = None, order: str = "change",
+                      top: Optional[int] = 20, max_buckets: int = 65536) -> dict:
+        """``trends`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The effective time
+        of a chunk's last line is carried into the next; the report is exactly the one-document
+        report, whatever the chunk size. A named pivot reads the source a second time, for its
+        timeline."""
+        from .trends import check_args, trends_stream
+        check_args(bucket_seconds, at, ratio, min_count, kind, order, max_buckets)
+        with _source(src_or_path) as src, self._engine_guard("trends"):
+            return trends_stream(self.engine, src, chunk_bytes, bucket_seconds, at, ratio, min_count, kind, order, top,
+                                 max_buckets)
+
+    def trends_resident(self, resident, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
+                        kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,
+                        max_buckets: int = 65536) -> dict:
+        """``trends`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        from .trends import check_args, trends_stream
+        check_args(bucket_seconds, at, ratio, min_count, kind, order, max_buckets)
+        with self._engine_guard("trends"):
+            return trends_stream(self.engine, resident, None, bucket_seconds, at, ratio, min_count, kind, order, top,
+                                 max_buckets)
 
     # ---- correlation report ------------------------------------------------------------------
     def correlate(self, logs, min_len: int = 8, top: Optional[int] = 20, order: str = "events", min_lines: int = 2,

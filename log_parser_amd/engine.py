@@ -903,6 +903,17 @@ class Engine:
         from .values import values_document
         return values_document(self, bytes(data), top, order, min_count, min_fill, varying)
 
+    # ------------------------------------------------------------------ trends report
+    def trends_bytes(self, data: bytes, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
+                     kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,
+                     max_buckets: int = 65536) -> dict:
+        """Which line templates of one document started, stopped or surged over its time?
+        (trends.py; ``golden.trends`` is the specification.) The matchers run only for the pivots
+        ``"first-event"`` / ``"first-error"`` (the document's timeline), nothing is scored and the
+        frequency window is not touched."""
+        from .trends import trends_document
+        return trends_document(self, bytes(data), bucket_seconds, at, ratio, min_count, kind, order, top, max_buckets)
+
     # ------------------------------------------------------------------ trace report
     def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
                      unexplained_only: bool = False) -> dict:

@@ -930,6 +930,221 @@ def values(logs, top: Optional[int] = 20, order: str = "peak", min_count: int = 
 
 
 # ---------------------------------------------------------------------------------------------
+# Trends report (an extra, as the gap report): what changed over the time of this log? The log's
+# own earlier part is the baseline: lines are counted per *cell* (template signature, time bucket),
+# a *pivot* bucket splits the log's span, and a template started, stopped, surged, faded or stayed
+# steady across it. No pattern and no baseline of healthy logs takes part. These functions are the
+# specification of ``log_parser_amd/trends.py`` and of the cell table (csrc/kernels/trends.hip,
+# cell_table.h).
+#
+# Known limits: only the stamps of ``line_timestamp`` count; an out-of-order stamp lands in whatever
+# bucket it names; the pivot has bucket granularity; two cells may share a 64-bit cell key; a
+# template is the first ``SIG_MAX_BYTES`` bytes of a line.
+
+TREND_KINDS = ("started", "stopped", "surged", "faded", "steady")
+TREND_UNDATED = -(1 << 63)      # the reserved bucket of a template's undated lines
+_TREND_MIX = 0x9E3779B97F4A7C15
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def trend_cell_key(sig: int, bucket: int) -> int:
+    """The 64-bit key of the cell (``sig``, ``bucket``): ``sig + bucket * _TREND_MIX`` mod 2^64. For
+    a fixed bucket it is a bijection of the signatures (``trend_cell_sig`` inverts it)."""
+    return (sig + bucket * _TREND_MIX) & _U64
+
+
+def trend_cell_sig(key: int, bucket: int) -> int:
+    """The signature whose cell in ``bucket`` has the key ``key``."""
+    return (key - bucket * _TREND_MIX) & _U64
+
+
+def trends_check_args(bucket_seconds=60, at=None, ratio: int = 4, min_count: int = 5, kind: Optional[str] = None,
+                      order: str = "change", max_buckets: int = 65536):
+    """(W in milliseconds, pivot source, pivot time in epoch ms or None), or ValueError. The pivot
+    source is ``"middle"`` (``at=None``), ``"given"`` (an int, or a string that ``line_timestamp``
+    parses from byte 0) or one of ``"first-event"`` / ``"first-error"`` (no time yet)."""
+    if isinstance(bucket_seconds, bool) or not isinstance(bucket_seconds, int) or bucket_seconds < 1:
+        raise ValueError("trends: bucket_seconds must be an integer >= 1")
+    if isinstance(max_buckets, bool) or not isinstance(max_buckets, int) or max_buckets < 1:
+        raise ValueError("trends: max_buckets must be an integer >= 1")
+    if isinstance(ratio, bool) or not isinstance(ratio, int) or ratio < 2:
+        raise ValueError("trends: ratio must be an integer >= 2")
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+        raise ValueError("trends: min_count must be an integer >= 1")
+    if kind is not None and kind != "all" and kind not in TREND_KINDS:
+        raise ValueError("trends: kind must be None, 'all' or one of %s" % ", ".join(TREND_KINDS))
+    if order not in ("change", "count", "first"):
+        raise ValueError("trends: order must be 'change', 'count' or 'first'")
+    W = 1000 * bucket_seconds
+    if at is None:
+        return W, "middle", None
+    if isinstance(at, bool):
+        raise ValueError("trends: at must be None, epoch milliseconds, a timestamp, 'first-event' or 'first-error'")
+    if isinstance(at, int):
+        return W, "given", at
+    if isinstance(at, (bytes, str)):
+        raw = at.encode("utf-8", errors="surrogateescape") if isinstance(at, str) else bytes(at)
+        if raw in (b"first-event", b"first-error"):
+            return W, raw.decode(), None
+        m = _STAMP.match(raw)
+        t = line_timestamp(raw) if m else None
+        if t is None:
+            raise ValueError("trends: at=%r is no timestamp" % (at,))
+        return W, "given", t
+    raise ValueError("trends: at must be None, epoch milliseconds, a timestamp, 'first-event' or 'first-error'")
+
+
+def trends_named_pivot(source: str, timeline_report: dict) -> int:
+    """Epoch milliseconds of the pivot ``"first-event"`` / ``"first-error"`` from the timeline
+    report of the same log and bucket width, or ValueError when the timeline has none."""
+    ref = timeline_report["firstEvent" if source == "first-event" else "firstErrorLine"]
+    if ref is None:
+        raise ValueError("trends: the log has no %s to take the pivot from"
+                         % ("dated event" if source == "first-event" else "dated error line"))
+    return line_timestamp(ref["timestamp"].encode("ascii"))
+
+
+def trends_pivot(source: str, at: Optional[int], b0: int, b1: int, W: int) -> Optional[int]:
+    """The pivot bucket p with ``b0 < p <= b1``: the middle ``b0 + nb // 2`` (None with fewer than
+    two buckets), or ``floor(at / W)`` -- ValueError when that lies outside ``(b0, b1]``."""
+    nb = b1 - b0 + 1
+    if source == "middle":
+        return b0 + nb // 2 if nb >= 2 else None
+    p = at // W
+    if not b0 < p <= b1:
+        raise ValueError("trends: the pivot %s (%s) is not behind the first bucket and within the span %s .. %s of the log"
+                         % (iso_ms(p * W), source, iso_ms(b0 * W), iso_ms(b1 * W)))
+    return p
+
+
+def trends_kind(before: int, after: int, nb_before: int, nb_after: int, ratio: int) -> str:
+    x, y = after * nb_before, before * nb_after
+    if before == 0:
+        return "started"
+    if after == 0:
+        return "stopped"
+    if x >= ratio * y:
+        return "surged"
+    if y >= ratio * x:
+        return "faded"
+    return "steady"
+
+
+def trends_listed(kind: Optional[str], k: str) -> bool:
+    """A template of the kind ``k`` is listed under the filter ``kind`` (None: all but steady)."""
+    return k != "steady" if kind is None else kind in ("all", k)
+
+
+def trends_lift(before: int, after: int, nb_before: int, nb_after: int) -> Fraction:
+    return Fraction((after + 1) * nb_before, (before + 1) * nb_after)
+
+
+def trends_order_key(order: str, lift: Fraction, dated: int, first: int):
+    """The sort key of a template: exact arithmetic (ints and ``Fraction``)."""
+    if order == "change":
+        return (-max(lift, 1 / lift), -dated, first)
+    if order == "count":
+        return (-dated, first)
+    return (first,)
+
+
+def trends_row(sig: int, lines: int, dated: int, before: int, after: int, first_bucket: int, last_bucket: int,
+               active: int, peak_bucket: int, peak_count: int, first: int, raw: bytes, W: int, kind: str,
+               lift: Fraction) -> dict:
+    """One row of the report from its numbers (``first``: the template's first line, 0-based) and
+    that line: ValueError unless the line has the template ``sig``."""
+    if line_signature(raw) != sig:
+        raise ValueError("trends: line %d does not have the template %016x" % (first + 1, sig))
+    return {"signature": "%016x" % sig, "kind": kind, "lift": float(lift), "lines": lines, "datedLines": dated,
+            "before": before, "after": after, "firstSeen": iso_ms(first_bucket * W), "lastSeen": iso_ms(last_bucket * W),
+            "activeBuckets": active, "peakBucket": iso_ms(peak_bucket * W), "peakCount": peak_count,
+            "firstLine": first + 1, "template": line_template(raw).decode("utf-8", errors="replace"),
+            "example": raw.decode("utf-8", errors="replace")}
+
+
+def trends_head(total: int, dated: int, templates: int, cells: int, bucket_seconds: int) -> dict:
+    """The report of a log before its span is known: the counts, no pivot, nothing listed."""
+    return {"totalLines": total, "datedLines": dated, "undatedLines": total - dated, "templates": templates,
+            "cells": cells, "bucketSeconds": bucket_seconds, "firstBucket": None, "lastBucket": None, "buckets": 0,
+            "pivot": None, "pivotSource": None, "bucketsBefore": 0, "bucketsAfter": 0,
+            "kinds": {k: 0 for k in TREND_KINDS}, "top": []}
+
+
+def trends(logs, pattern_sets: Optional[List[PatternSet]] = None, params: Optional[ScoringParams] = None,
+           bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5, kind: Optional[str] = None,
+           order: str = "change", top: Optional[int] = 20, max_buckets: int = 65536) -> dict:
+    """The trends report of ``logs`` (str or bytes). A line's effective time is its own stamp, else
+    the stamp of the nearest earlier stamped line (``timeline``'s fill); its bucket is
+    ``floor(eff / W)`` with ``W = 1000 * bucket_seconds``. The span ``b0 .. b1`` covers the buckets
+    of all dated lines (ValueError beyond ``max_buckets``); the pivot p (``trends_pivot``; the
+    named pivots come from ``timeline`` with ``pattern_sets`` / ``params``) splits it into
+    ``p - b0`` buckets before and ``b1 - p + 1`` from p on. Per template: ``lines``,
+    ``datedLines``, ``before`` / ``after`` (dated lines in buckets ``< p`` / ``>= p``),
+    ``firstSeen`` / ``lastSeen`` (start of its first / last dated bucket), ``activeBuckets``,
+    ``peakBucket`` / ``peakCount`` (its largest dated cell, the earliest on a tie), ``kind``
+    (``trends_kind``), ``lift`` (``trends_lift``), its first line and that line as the example.
+    Listed are the templates with ``datedLines >= min_count`` of the kind ``kind`` (None: all but
+    steady), in ``order`` (``trends_order_key``). ``cells`` counts the (template, bucket) pairs,
+    the undated lines of a template as one more; ``kinds`` the templates with ``datedLines >=
+    min_count`` per kind."""
+    W, source, at_ms = trends_check_args(bucket_seconds, at, ratio, min_count, kind, order, max_buckets)
+    raws = [line.encode("utf-8", errors="surrogateescape") for line in split_lines(_as_text(logs))]
+    cells: Dict[tuple, int] = {}
+    first: Dict[int, int] = {}
+    cur = None
+    n_dated = 0
+    for i, raw in enumerate(raws):
+        t = line_timestamp(raw)
+        cur = cur if t is None else t
+        sig = line_signature(raw)
+        first.setdefault(sig, i)
+        b = TREND_UNDATED if cur is None else cur // W
+        n_dated += cur is not None
+        cells[(sig, b)] = cells.get((sig, b), 0) + 1
+    out = trends_head(len(raws), n_dated, len(first), len(cells), bucket_seconds)
+    dated = [b for _, b in cells if b != TREND_UNDATED]
+    if not dated:
+        return out
+    b0, b1 = min(dated), max(dated)
+    if b1 - b0 + 1 > max_buckets:
+        raise timeline_span_error(b0 * W, b1 * W, W, max_buckets)
+    out.update({"firstBucket": iso_ms(b0 * W), "lastBucket": iso_ms(b1 * W), "buckets": b1 - b0 + 1})
+    if source in ("first-event", "first-error"):
+        at_ms = trends_named_pivot(source, timeline(logs, pattern_sets or [], params or ScoringParams(),
+                                                    bucket_seconds, max_buckets))
+    p = trends_pivot(source, at_ms, b0, b1, W)
+    if p is None:
+        return out
+    nb_before, nb_after = p - b0, b1 - p + 1
+    out.update({"pivot": iso_ms(p * W), "pivotSource": source, "bucketsBefore": nb_before, "bucketsAfter": nb_after})
+    per: Dict[int, Dict[int, int]] = {}
+    for (sig, b), c in cells.items():
+        per.setdefault(sig, {})[b] = c
+    listed = []
+    for sig, row in per.items():
+        lines = sum(row.values())
+        row = {b: c for b, c in row.items() if b != TREND_UNDATED}
+        n = sum(row.values())
+        if n < min_count:
+            continue
+        before = sum(c for b, c in row.items() if b < p)
+        k = trends_kind(before, n - before, nb_before, nb_after, ratio)
+        out["kinds"][k] += 1
+        if not trends_listed(kind, k):
+            continue
+        lift = trends_lift(before, n - before, nb_before, nb_after)
+        peak = max(row.values())
+        listed.append((trends_order_key(order, lift, n, first[sig]),
+                       (sig, lines, n, before, n - before, min(row), max(row), len(row),
+                        min(b for b, c in row.items() if c == peak), peak, first[sig], raws[first[sig]], W, k, lift)))
+    listed.sort(key=lambda kv: kv[0])
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    out["top"] = [trends_row(*row) for _, row in listed]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Trace report (an extra, as the gap report): which stack traces does a log hold, how often, where
 # first, with which root cause, and does any pattern explain them? These functions are the
 # specification of ``log_parser_amd/traces.py`` and of the line classifier and the run scan

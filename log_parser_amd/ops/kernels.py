@@ -1057,6 +1057,108 @@ class GapTable:
 
 
 # ---------------------------------------------------------------------------------------------
+# cell table of the trends report (csrc/kernels/trends.hip, cell_table.h)
+
+CT_UNDATED = -(1 << 63)     # the bucket of lines without an effective time
+CT_TILE = 2048              # lines per block of k_cell_fold at most
+CT_LDS_SLOTS = 1024         # slots of its LDS table: more distinct cells in a tile go to HBM directly
+
+
+class CellTable:
+    """Device-resident counts per cell (template signature, time bucket): per cell its lines and
+    its smallest global line number, kept across ``fold`` calls (the chunks of a stream). The key
+    column holds ``golden.trend_cell_key(sig, bucket)``. GPU: k_cell_fold / k_cell_rows /
+    k_cell_reinsert; CPU: their host twins on the same layout. Capacity rule, growth and the host
+    bound of ``used`` are ``GapTable``'s."""
+
+    def __init__(self, device, cap: int = 1 << 12, tile: int = 0):
+        """``tile``: lines per block of k_cell_fold (256..CT_TILE, a multiple of 256) instead of
+        the size the launch picks from its number of lines (tests)."""
+        cap = max(2, int(cap))
+        self.tile = int(tile)
+        if self.tile and (self.tile < 256 or self.tile > CT_TILE or self.tile % 256):
+            raise ValueError("CellTable: tile must be 256..%d, a multiple of 256" % CT_TILE)
+        if cap & (cap - 1):
+            raise ValueError("CellTable: cap must be a power of two")
+        self.device = torch.device(device)
+        self._bound = 0             # host upper bound of the occupied slots
+        self._alloc(cap)
+
+    def _alloc(self, cap: int) -> None:
+        dev = self.device
+        self.cap = cap
+        self._key = torch.full((cap + 1,), GT_EMPTY, dtype=torch.int64, device=dev)
+        self._key[cap] = 0          # the side slot of the cell whose key equals the marker: unclaimed
+        self._sig = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._bucket = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._first = torch.full((cap + 1,), _I64_MAX, dtype=torch.int64, device=dev)
+        self._used = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def _tab(self):
+        return (self._key.data_ptr(), self._sig.data_ptr(), self._bucket.data_ptr(), self._count.data_ptr(),
+                self._first.data_ptr(), self._used.data_ptr(), self.cap)
+
+    @property
+    def _cuda(self) -> bool:
+        return self.device.type == "cuda"
+
+    @property
+    def used(self) -> int:
+        """Occupied slots (a read of the device counter)."""
+        used, lost = self._used.tolist()
+        if lost:
+            raise RuntimeError("CellTable: %d lines found no slot (capacity rule broken)" % lost)
+        self._bound = used
+        return used
+
+    def rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(signature, bucket, lines, smallest line) of every cell, int64 each, in no particular
+        order; the bucket of a template's undated lines is ``CT_UNDATED``."""
+        n = self.used
+        cols = tuple(torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(4))
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        N.cell_rows(self._tab(), tuple(c.data_ptr() for c in cols), n, cnt.data_ptr(), _s(self._key), self._cuda)
+        if int(cnt.item()) != n:
+            raise RuntimeError("CellTable: %d occupied slots, the counter says %d" % (int(cnt.item()), n))
+        return cols
+
+    def _grow(self, cap: int) -> None:
+        rows = self.rows()
+        used = rows[0].numel()
+        self._alloc(cap)
+        if used:
+            N.cell_reinsert(self._tab(), tuple(c.data_ptr() for c in rows), used, _s(self._key), self._cuda)
+            self._used[0] = used
+
+    def fold(self, sig: torch.Tensor, eff: torch.Tensor, line_base: int, W: int) -> None:
+        """Fold n consecutive lines into the table: line i has the signature ``sig[i]``, the
+        effective time ``eff[i]`` (``TS_NONE``: undated) and the global number ``line_base + i``;
+        its cell is (sig[i], floor(eff[i] / W))."""
+        n = sig.numel()
+        if eff.numel() != n:
+            raise ValueError("CellTable.fold: sig and eff differ in length")
+        if isinstance(W, bool) or int(W) < 1:
+            raise ValueError("CellTable.fold: W must be >= 1")
+        if not 0 <= int(line_base) <= _I64_MAX - n:
+            raise ValueError("CellTable.fold: line_base out of range")
+        if n == 0:
+            return
+        sig = sig.to(device=self.device, dtype=torch.int64).contiguous()
+        eff = eff.to(device=self.device, dtype=torch.int64).contiguous()
+        if 2 * (self._bound + n) > self.cap:
+            used = self.used                                    # the bound crossed the limit: the real count
+            if 2 * (used + n) > self.cap:
+                cap = self.cap
+                while 2 * (used + n) > cap:
+                    cap *= 2
+                self._grow(cap)
+        self._bound += n
+        N.cell_fold(self._tab(), sig.data_ptr(), eff.data_ptr(), n, int(line_base), int(W), _s(self._key), self._cuda,
+                    self.tile)
+
+
+# ---------------------------------------------------------------------------------------------
 # novelty report (csrc/kernels/novelty.hip): the lines whose template a baseline table does not hold
 
 NV_MAX_LINES = 2048         # lines per block of k_novel_sig at most
@@ -1260,6 +1362,33 @@ def line_timestamps(text, line_start, line_len) -> torch.Tensor:
         N.ts_parse(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, out.data_ptr(),
                    _s(text), text.is_cuda)
     return out
+
+
+LS_MAX_LINES = 2048         # lines per block of k_line_stamps at most (csrc/kernels/trends.hip)
+
+
+def line_stamps(text, line_start, line_len, per_block: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(sig int64[L], ts int64[L]): template signature (``golden.line_signature``) and stamp
+    (``golden.line_timestamp``, ``TS_NONE`` where the line has none) of every line from ONE visit
+    of the line -- what ``line_signatures`` and ``line_timestamps`` give in two launches.
+    k_line_stamps or its host twin. ``per_block``: lines per block instead of the size the launch
+    picks (tests)."""
+    L = line_start.numel()
+    if line_start.dtype != torch.int64 or not line_start.is_contiguous():
+        raise ValueError("line_stamps: line_start must be contiguous int64[L]")
+    if line_len.dtype != torch.int32 or line_len.numel() != L or not line_len.is_contiguous():
+        raise ValueError("line_stamps: line_len must be contiguous int32[L]")
+    if text.dtype != torch.uint8 or not text.is_contiguous() or line_start.device != text.device \
+            or line_len.device != text.device:
+        raise ValueError("line_stamps: text must be contiguous uint8, the line index on its device")
+    if per_block and not 0 < per_block <= LS_MAX_LINES:
+        raise ValueError("line_stamps: per_block must be 1..%d" % LS_MAX_LINES)
+    sig = torch.empty(L, dtype=torch.int64, device=text.device)
+    ts = torch.empty(L, dtype=torch.int64, device=text.device)
+    if L:
+        N.line_stamps(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, sig.data_ptr(),
+                      ts.data_ptr(), _s(text), text.is_cuda, per_block)
+    return sig, ts
 
 
 def timeline_fill(ts: torch.Tensor, carry_last: int = TS_NONE,

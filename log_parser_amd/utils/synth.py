@@ -8,6 +8,7 @@ pattern triggers are planted at a controlled rate.
 from __future__ import annotations
 
 import random
+from datetime import datetime, timedelta
 from typing import Dict, List, Optional, Tuple
 
 from ..models.schema import PatternSet
@@ -413,7 +414,53 @@ def metric_log(n_lines: int, templates: List[str], seed: int = 0, burst_at: floa
     return "".join(line + "\n" for line in lines), burst
 
 
-CORRELATED_FAIL = "request aborted: upstream deadline exceeded"     # what the last line of a failing request says
+TREND_T0_MS = 1758283200000         # 2025-09-19T12:00:00Z
+TREND_STOPPED = "INFO  [lease] heartbeat: renewed leader lease, sequence %d"
+TREND_STARTED = "ERROR [net] connection reset by peer while reading from upstream %d"
+TREND_SURGED = "WARN  [gc] pause of %dms exceeded the budget"
+
+
+def trend_log(n_lines: int, templates: List[str], seed: int = 0, step_ms: int = 100,
+              change_at: float = 0.75) -> Tuple[str, Tuple[str, str, str]]:
+    """A log whose content changes at one line: line ``i`` is stamped ``TREND_T0_MS + i *
+    step_ms`` (a clock of its own that never wraps). The bulk is ``templates``
+    (``log_templates``) with the skewed weights of ``templated_log``; about 3 % of the lines are
+    unstamped ``\\tat ...`` frames. Three templates are planted around the change line ``c`` =
+    ``change_at * n_lines``, moved down to a whole minute of the clock where that leaves a line
+    before it (so it is a bucket boundary of every width that divides a minute): a heartbeat on
+    every 20th line before ``c`` and never after, an error on about 5 % of the lines from ``c`` on
+    and never before, and a line on about 1 % of the lines before and 10 % after. Returns (text,
+    (the heartbeat, the error, the surging line)) -- each as it stands in the log behind the stamp,
+    with its number field still ``%d``."""
+    rng = random.Random(seed)
+    weights = [1.0 / (k + 1) for k in range(len(templates))]
+    c = int(change_at * n_lines)
+    per_minute = max(1, 60000 // step_ms)
+    if c // per_minute:
+        c = c // per_minute * per_minute
+    epoch = datetime(1970, 1, 1)
+    parts = []
+    for i, t in enumerate(rng.choices(templates, weights=weights, k=n_lines)):
+        d = epoch + timedelta(milliseconds=TREND_T0_MS + i * step_ms)
+        stamp = "%04d-%02d-%02dT%02d:%02d:%02d.%03dZ " % (d.year, d.month, d.day, d.hour, d.minute, d.second,
+                                                          d.microsecond // 1000)
+        r = rng.random()
+        if i < c and i % 20 == 0:
+            line = stamp + TREND_STOPPED % (i // 20)
+        elif r < 0.03:
+            line = "\tat com.example.worker.Task.run(Task.java:%d)" % rng.randrange(10, 400)
+        elif i >= c and r < 0.08:
+            line = stamp + TREND_STARTED % rng.randrange(1, 64)
+        elif r >= 1.0 - (0.01 if i < c else 0.10):
+            line = stamp + TREND_SURGED % rng.randrange(200, 5000)
+        else:
+            body = t.split(" ", 1)[1]       # (behind the template's own stamp)
+            line = stamp + body % tuple(rng.randrange(1, 1 << 20) for _ in range(body.count("%")))
+        parts.append(line + "\n")
+    return "".join(parts), (TREND_STOPPED, TREND_STARTED, TREND_SURGED)
+
+
+CORRELATED_FAIL ="request aborted: upstream deadline exceeded"     # what the last line of a failing request says
 
 
 def correlated_log(n_lines: int, templates: List[str], n_requests: int, seed: int = 0, fail_rate: float = 0.25,
