@@ -1318,6 +1318,30 @@ PYBIND11_MODULE(_lpnative, m) {
     py::gil_scoped_release nogil;
     cell_reinsert_host(T, R, n); },
         py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
+  // ---- pauses report (pauses.hip): the steps between stamped lines; count first, then the rows
+  m.def("pause_tmp_words", &pause_tmp_words, py::arg("L"));
+  m.def("pause_scan", [](bool emit, uint64_t ts, uint64_t sig, int64_t L, int64_t line_base, int64_t min_ms,
+                         int64_t carry_ts, int64_t carry_line, int64_t carry_sig, uint64_t tmp, uint64_t head,
+                         py::tuple rows, int64_t cap, uint64_t stats, uint64_t hist, uint64_t s, bool dev) {
+    PauseArgs A;
+    A.ts = P<const int64_t>(ts); A.sig = P<const int64_t>(sig); A.L = L;
+    A.line_base = line_base; A.min_ms = min_ms;
+    A.carry_ts = carry_ts; A.carry_line = carry_line; A.carry_sig = carry_sig;
+    A.tmp = P<int64_t>(tmp); A.head = P<int64_t>(head);
+    if (rows.size() != 5) throw std::runtime_error("pause_scan: rows must be 5 columns");
+    A.rows = PauseRows{P<int64_t>(rows[0].cast<uint64_t>()), P<int64_t>(rows[1].cast<uint64_t>()),
+                       P<int64_t>(rows[2].cast<uint64_t>()), P<int64_t>(rows[3].cast<uint64_t>()),
+                       P<int64_t>(rows[4].cast<uint64_t>())};
+    A.cap = cap; A.stats = P<int64_t>(stats); A.hist = P<int64_t>(hist);
+    if (dev) {
+      if (emit) pause_emit_dev(A, s); else pause_count_dev(A, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    if (emit) pause_emit_host(A); else pause_count_host(A); },
+        py::arg("emit"), py::arg("ts"), py::arg("sig"), py::arg("L"), py::arg("line_base"), py::arg("min_ms"),
+        py::arg("carry_ts"), py::arg("carry_line"), py::arg("carry_sig"), py::arg("tmp"), py::arg("head"),
+        py::arg("rows"), py::arg("cap"), py::arg("stats"), py::arg("hist"), py::arg("stream"), py::arg("dev"));
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

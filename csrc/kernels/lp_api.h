@@ -589,6 +589,44 @@ void cell_rows_host(const CellTab& T, const CellRows& R, int64_t out_cap, unsign
 void cell_reinsert_host(const CellTab& T, const CellRows& R, int64_t n);
 }  // namespace lp
 
+// ---- pauses report (pauses.hip): the steps between the stamped lines of a log, the long ones as rows
+namespace lp {
+constexpr int PS_BUCKETS = 64;      // interval histogram: bucket = bit length of the step (0 for 0)
+// columns of the statistics: sums are added to, the smallest / largest stamp lowered / raised
+// (start: 0, 0, 0, INT64_MAX, INT64_MIN)
+enum { PS_STAMPED = 0, PS_BACKWARD = 1, PS_PAUSED_MS = 2, PS_MIN_TS = 3, PS_MAX_TS = 4, PS_STATS = 5 };
+struct PauseRows {           // one row per pause, in line order
+  int64_t* to_line; int64_t* from_line;      // global line numbers
+  int64_t* ms;                               // the step
+  int64_t* from_sig; int64_t* to_sig;        // the two lines' template signatures
+};
+struct PauseArgs {
+  const int64_t* ts;         // [L] stamp of every line or TS_NONE, within +-2^61
+  const int64_t* sig;        // [L] template signature of every line
+  int64_t L;
+  int64_t line_base;         // global number of line 0
+  int64_t min_ms;            // >= 1: a step >= min_ms is a pause
+  // the last stamped line of the earlier runs: its stamp (TS_NONE: none), its global line
+  // (< line_base) and its signature
+  int64_t carry_ts, carry_line, carry_sig;
+  int64_t* tmp;              // device: pause_tmp_words(L) words, written by pause_count_dev, read by pause_emit_dev
+  // pause_count: [0] the pauses of this run, [1..3] stamp, line, signature of the last stamped
+  // line so far (TS_NONE, -1, 0: still none)
+  int64_t* head;
+  // pause_emit: the first `cap` rows; stats[PS_STATS] and hist[PS_BUCKETS] are added to
+  PauseRows rows;
+  int64_t cap;
+  int64_t* stats;
+  int64_t* hist;
+};
+int64_t pause_tmp_words(int64_t L);
+// two calls per run, so that the caller can size the rows from head[0] in between; L = 0 launches nothing
+void pause_count_dev(const PauseArgs& A, uint64_t stream);
+void pause_emit_dev(const PauseArgs& A, uint64_t stream);
+void pause_count_host(const PauseArgs& A);
+void pause_emit_host(const PauseArgs& A);
+}  // namespace lp
+
 // ---- trace report (traces.hip): stack traces as runs of frame / cause lines, one row per trace
 #include "trace_core.h"
 namespace lp {

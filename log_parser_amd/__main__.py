@@ -47,6 +47,11 @@
                                                the line templates of a log that started, stopped,
                                                surged or faded across a pivot in the log's own
                                                time: what changed (JSON)
+  pauses    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--min-ms N]
+            [--by before|after] [--order total|max|count|share|first] [--min-count N] [--top N]
+                                               where the log went silent: the steps between its
+                                               stamped lines, the long ones with the lines around
+                                               them and grouped by the template in front (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -241,6 +246,21 @@ def cmd_trends(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_pauses(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    kw = {"min_ms": args.min_ms, "by": args.by, "order": args.order, "min_count": args.min_count, "top": args.top}
+    try:
+        if args.stream:
+            rep = lp.pauses_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.pauses_file(args.file, **kw)
+    except ValueError as e:                 # a threshold or a count out of range
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -355,13 +375,28 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="largest change of rate first (default), most dated lines first, or in order of first "
                         "appearance")
     d.add_argument("--top", type=int, default=20, help="templates reported (default 20)")
+    q = sub.add_parser("pauses", help="where a log file went silent, and after which line templates")
+    q.add_argument("file")
+    _library_options(q)
+    q.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    q.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    q.add_argument("--min-ms", type=int, default=1000, metavar="N",
+                   help="a step of at least N milliseconds between two stamped lines is a pause (default 1000)")
+    q.add_argument("--by", choices=("before", "after"), default="before",
+                   help="group the pauses by the template of the line before them (default) or after them")
+    q.add_argument("--order", choices=("total", "max", "count", "share", "first"), default="total",
+                   help="most paused time first (default), longest pause first, most pauses first, largest share of "
+                        "the template's lines first, or in order of the first pause")
+    q.add_argument("--min-count", type=int, default=1, metavar="N",
+                   help="list only the templates with at least N pauses (default 1)")
+    q.add_argument("--top", type=int, default=20, help="pauses and templates reported (default 20)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
             "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values,
-            "trends": cmd_trends}[args.cmd](args, cfg)
+            "trends": cmd_trends, "pauses": cmd_pauses}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

@@ -43,6 +43,7 @@ SOURCES = [
     ("kernels/values.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("kernels/trends.hip", "hip"),
+    ("kernels/pauses.hip", "hip"),
     ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),

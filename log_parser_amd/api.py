@@ -44,6 +44,10 @@ to embedders, with what an in-process user needs beyond one call at a time:
   faded across a pivot in its own time -- ``golden.trends``; ``trends_stream`` /
   ``trends_resident`` for one log too large for one piece, ``trend_accumulator`` for a log that
   arrives over time;
+* ``pauses`` / ``pauses_file``: where a log went silent -- the steps between its stamped lines, the
+  long ones with the lines around them and grouped by the template in front of them --
+  ``golden.pauses``; ``pauses_stream`` / ``pauses_resident`` for one log too large for one piece,
+  ``pause_accumulator`` for a log that arrives over time;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -558,6 +562,71 @@ class LogParser:
         with self._engine_guard("trends"):
             return trends_stream(self.engine, resident, None, bucket_seconds, at, ratio, min_count, kind, order, top,
                                  max_buckets)
+
+    # ---- pauses report -----------------------------------------------------------------------
+    def pauses(self, logs, min_ms: int = 1000, by: str = "before", order: str = "total", min_count: int = 1,
+               top: Optional[int] = 20) -> dict:
+        """Where did one document (str or bytes) go silent, and after which line templates? The
+        step between two neighbouring stamped lines is the later stamp minus the earlier; a step
+        below 0 is only counted (``backwardSteps``), a step of at least ``min_ms`` milliseconds is
+        a pause. The head holds the counts, the exact sum ``pausedMs`` and its share of the log's
+        span; ``intervals`` the steps >= 0 by size (bucket b holds ``[2^(b-1), 2^b)`` ms): the
+        log's usual cadence next to its outliers; ``longest`` the ``top`` pauses with the line
+        before and the line after; ``templates`` the pauses grouped by the template of the line
+        before them (``by="before"``: what was running when it went quiet) or after them
+        (``"after"``: what woke up), with ``pauses``, ``lines``, ``share``, ``totalMs``,
+        ``maxMs``, ``maxLine``, ``firstLine`` and an example; groups below ``min_count`` pauses
+        are dropped. ``order``: ``"total"`` (most paused time first), ``"max"``, ``"count"``,
+        ``"share"`` or ``"first"``; ``top=None``: every pause and every template. No pattern
+        takes part. ``Engine.pauses_bytes``; ``golden.pauses`` is the specification; the
+        frequency window is not touched."""
+        from .pauses import check_args, check_top
+        check_args(min_ms, by, order, min_count)
+        check_top(top)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("pauses"):
+            return self.engine.pauses_bytes(logs, min_ms=min_ms, by=by, order=order, min_count=min_count, top=top)
+
+    def pauses_file(self, path: str, min_ms: int = 1000, by: str = "before", order: str = "total", min_count: int = 1,
+                    top: Optional[int] = 20) -> dict:
+        """``pauses`` of a log file, read as ONE document whatever its size."""
+        from .pauses import check_args, check_top
+        check_args(min_ms, by, order, min_count)
+        check_top(top)
+        with open(path, "rb") as f:
+            return self.pauses(f.read(), min_ms=min_ms, by=by, order=order, min_count=min_count, top=top)
+
+    def pause_accumulator(self, min_ms: int = 1000, by: str = "before", longest: Optional[int] = 20):
+        """A ``pauses.PauseAccumulator`` on this parser's engine for a log that arrives over time
+        (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then ``report``);
+        each of its calls runs under the batcher guard and the lock of ``pauses``. ``longest``:
+        how many of the longest pauses it keeps (None: all), the limit of ``report(top=...)``."""
+        from .pauses import PauseAccumulator
+        with self._engine_guard("pauses"):
+            return PauseAccumulator(self.engine, min_ms, by, longest, guard=lambda: self._engine_guard("pauses"))
+
+    def pauses_stream(self, src_or_path, chunk_bytes: Optional[int] = None, min_ms: int = 1000, by: str = "before",
+                      order: str = "total", min_count: int = 1, top: Optional[int] = 20) -> dict:
+        """``pauses`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The last stamped
+        line of a chunk is carried into the next; the report is exactly the one-document report,
+        whatever the chunk size."""
+        from .pauses import check_args, check_top
+        check_args(min_ms, by, order, min_count)
+        acc = self.pause_accumulator(min_ms, by, check_top(top))
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(order, min_count, top)
+
+    def pauses_resident(self, resident, min_ms: int = 1000, by: str = "before", order: str = "total",
+                        min_count: int = 1, top: Optional[int] = 20) -> dict:
+        """``pauses`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        from .pauses import check_args, check_top
+        check_args(min_ms, by, order, min_count)
+        acc = self.pause_accumulator(min_ms, by, check_top(top))
+        acc.add_resident(resident)
+        return acc.report(order, min_count, top)
 
     # ---- correlation report ------------------------------------------------------------------
     def correlate(self, logs, min_len: int = 8, top: Optional[int] = 20, order: str = "events", min_lines: int = 2,

@@ -914,6 +914,15 @@ class Engine:
         from .trends import trends_document
         return trends_document(self, bytes(data), bucket_seconds, at, ratio, min_count, kind, order, top, max_buckets)
 
+    # ------------------------------------------------------------------ pauses report
+    def pauses_bytes(self, data: bytes, min_ms: int = 1000, by: str = "before", order: str = "total",
+                     min_count: int = 1, top: Optional[int] = 20) -> dict:
+        """Where did one document go silent, and after which line templates? (pauses.py;
+        ``golden.pauses`` is the specification.) The matchers do not run, nothing is scored and
+        the frequency window is not touched."""
+        from .pauses import pauses_document
+        return pauses_document(self, bytes(data), min_ms, by, order, min_count, top)
+
     # ------------------------------------------------------------------ trace report
     def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
                      unexplained_only: bool = False) -> dict:

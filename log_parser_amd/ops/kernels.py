@@ -1411,6 +1411,68 @@ def timeline_fill(ts: torch.Tensor, carry_last: int = TS_NONE,
     return eff, ooo
 
 
+PS_TILE = 2048              # lines per block of k_ps_tiles / k_ps_emit (csrc/kernels/pauses.hip)
+PS_BUCKETS = 64             # interval histogram: bucket = bit length of the step
+PS_STAMPED, PS_BACKWARD, PS_PAUSED_MS, PS_MIN_TS, PS_MAX_TS = range(5)     # columns of its statistics
+PS_MAX_ABS_TS = 1 << 61     # stamps lie within +-2^61, so that no step overflows
+
+
+def pause_stats(device) -> torch.Tensor:
+    """Statistics of no line at all: what ``pause_scan`` adds a run to."""
+    return torch.tensor([0, 0, 0, _I64_MAX, -_I64_MAX - 1], dtype=torch.int64, device=device)
+
+
+def pause_scan(ts: torch.Tensor, sig: torch.Tensor, min_ms: int, line_base: int = 0, carry=None,
+               stats: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None):
+    """The steps between the stamped lines of a run (``ts`` / ``sig``: int64[L], what
+    ``line_stamps`` gives; line i has the global number ``line_base + i``). ``carry``: None, or
+    (stamp, global line, signature) of the last stamped line of the earlier runs. Returns
+
+    * rows: (to_line, from_line, ms, from_sig, to_sig), int64[m] each: the steps ``>= min_ms``,
+      in line order;
+    * stats int64[5] on the device: stamped lines, backward steps, the sum of the rows' ms,
+      smallest and largest stamp (``pause_stats``: none). With ``stats`` given the run is added
+      to that tensor, which is returned;
+    * hist int64[64]: the steps >= 0 by bit length (``hist`` given: added to it);
+    * the new carry (None: still no stamped line).
+
+    k_ps_tiles / k_ps_prefix / k_ps_emit or their host twin; the row count and the carry are
+    the one read in between. Nothing is launched at L = 0."""
+    dev = ts.device
+    if ts.dtype != torch.int64 or not ts.is_contiguous() or ts.dim() != 1:
+        raise ValueError("pause_scan: ts must be contiguous int64[L]")
+    L = ts.numel()
+    if sig.dtype != torch.int64 or sig.numel() != L or not sig.is_contiguous() or sig.device != dev:
+        raise ValueError("pause_scan: sig must be contiguous int64[L] on the device of ts")
+    if isinstance(min_ms, bool) or not isinstance(min_ms, int) or not 1 <= min_ms <= _I64_MAX:
+        raise ValueError("pause_scan: min_ms must be an integer >= 1")
+    if isinstance(line_base, bool) or not isinstance(line_base, int) or not 0 <= line_base <= _I64_MAX - L:
+        raise ValueError("pause_scan: line_base out of range")
+    if carry is not None:
+        c_ts, c_line, c_sig = (int(x) for x in carry)
+        if not -PS_MAX_ABS_TS <= c_ts <= PS_MAX_ABS_TS or not 0 <= c_line < line_base:
+            raise ValueError("pause_scan: the carry is (stamp within +-2^61, line before line_base, signature)")
+    else:
+        c_ts, c_line, c_sig = TS_NONE, -1, 0
+    for name, t, n in (("stats", stats, 5), ("hist", hist, PS_BUCKETS)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous() or t.device != dev):
+            raise ValueError("pause_scan: %s must be contiguous int64[%d] on the device of ts" % (name, n))
+    stats = pause_stats(dev) if stats is None else stats
+    hist = torch.zeros(PS_BUCKETS, dtype=torch.int64, device=dev) if hist is None else hist
+    if L == 0:
+        return tuple(torch.empty(0, dtype=torch.int64, device=dev) for _ in range(5)), stats, hist, carry
+    tmp = torch.empty(N.pause_tmp_words(L), dtype=torch.int64, device=dev) if ts.is_cuda else None
+    head = torch.empty(4, dtype=torch.int64, device=dev)
+    none = (0, 0, 0, 0, 0)
+    args = (ts.data_ptr(), sig.data_ptr(), L, line_base, min_ms, c_ts, c_line, c_sig, _p(tmp), head.data_ptr())
+    N.pause_scan(False, *args, none, 0, 0, 0, _s(ts), ts.is_cuda)
+    m, n_ts, n_line, n_sig = head.tolist()
+    rows = tuple(torch.empty(m, dtype=torch.int64, device=dev) for _ in range(5))
+    N.pause_scan(True, *args, tuple(r.data_ptr() for r in rows), m, stats.data_ptr(), hist.data_ptr(), _s(ts),
+                 ts.is_cuda)
+    return rows, stats, hist, (None if n_ts == TS_NONE else (n_ts, n_line, n_sig))
+
+
 def timeline_hist(eff: torch.Tensor, feat: torch.Tensor, ev_line: torch.Tensor, ev_pat: torch.Tensor,
                   sev_index: torch.Tensor, t0: int, W: int, nb: int, S: int) -> torch.Tensor:
     """int64[nb, 3 + S]: per bucket ``[t0 + b * W, t0 + (b + 1) * W)`` the lines whose effective

@@ -460,6 +460,51 @@ def trend_log(n_lines: int, templates: List[str], seed: int = 0, step_ms: int = 
     return "".join(parts), (TREND_STOPPED, TREND_STARTED, TREND_SURGED)
 
 
+PAUSE_BEFORE = "INFO  [pool] waiting for a free connection, %d in use"      # what the log says before it goes quiet
+PAUSE_AFTER = "WARN  [pool] connection acquired after a wait, attempt %d"     # and when it wakes up
+
+
+def pause_log(n_lines: int, templates: List[str], seed: int = 0, pauses: int = 6) -> Tuple[str, List[Tuple[int, int, int]]]:
+    """A log with planted silences. Stamped lines follow each other by 1..400 ms (a clock of its
+    own from ``TREND_T0_MS`` that never wraps); about 3 % of the lines are unstamped ``\\tat ...``
+    frames. At ``pauses`` places, spread over the log, a ``PAUSE_BEFORE`` line is followed --
+    behind 0..2 unstamped frames -- by a ``PAUSE_AFTER`` line whose stamp is 5 s, 7 s, 9 s ...
+    later, a different length at every place. The bulk is ``templates`` (``log_templates``) with
+    the skewed weights of ``templated_log``. Returns (text, [(ms, from-line, to-line), ...] of the
+    planted pauses, lines 0-based, the longest first) -- known by construction."""
+    rng = random.Random(seed)
+    weights = [1.0 / (k + 1) for k in range(len(templates))]
+    places = {(k + 1) * n_lines // (pauses + 1): k for k in range(pauses)} if n_lines > 4 * pauses else {}
+    epoch = datetime(1970, 1, 1)
+    t = TREND_T0_MS
+    parts: List[str] = []
+    planted: List[Tuple[int, int, int]] = []
+    pending = None                      # (ms, from-line): the silence the next stamped line ends
+    frames = 0                          # unstamped lines still to come inside it
+    bulk = iter(rng.choices(templates, weights=weights, k=n_lines))
+    for i in range(n_lines):
+        body = next(bulk).split(" ", 1)[1]      # (behind the template's own stamp)
+        if frames or (pending is None and i not in places and i and rng.random() < 0.03):
+            frames = max(0, frames - 1)
+            parts.append("\tat com.example.worker.Task.run(Task.java:%d)\n" % rng.randrange(10, 400))
+            continue
+        if pending is not None:
+            t += pending[0]
+            planted.append((pending[0], pending[1], i))
+            line, pending = PAUSE_AFTER % rng.randrange(1, 9), None
+        elif i in places:
+            t += rng.randrange(1, 401)
+            pending, frames = (5000 + 2000 * places[i], i), places[i] % 3
+            line = PAUSE_BEFORE % rng.randrange(1, 64)
+        else:
+            t += rng.randrange(1, 401)
+            line = body % tuple(rng.randrange(1, 1 << 20) for _ in range(body.count("%")))
+        d = epoch + timedelta(milliseconds=t)
+        parts.append("%04d-%02d-%02dT%02d:%02d:%02d.%03dZ %s\n" % (d.year, d.month, d.day, d.hour, d.minute, d.second,
+                                                                  d.microsecond // 1000, line))
+    return "".join(parts), sorted(planted, reverse=True)
+
+
 CORRELATED_FAIL ="request aborted: upstream deadline exceeded"     # what the last line of a failing request says
 
 
