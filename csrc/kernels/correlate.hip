@@ -15,16 +15,11 @@
 #include "gap_table.h"
 #include "key_core.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 
 namespace lp {
-
-#define LP_KCHECK(x)                                                                                            \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
 
 constexpr int KL_MAX_LINES = 2048;                  // lines per block at most
 constexpr int KL_ROUND = 256;                       // lines per round: one per lane
@@ -37,17 +32,17 @@ __device__ __forceinline__ int64_t kl_line(const KeyLinesArgs& A, int64_t i) {
   return (x >= 0 && x < A.nl) ? x : -1;
 }
 
-// A block owns `per_block` consecutive items (k_lead_sig's structure), one lane per line and round.
-// A round's lanes hold 0..8 pairs each: an exclusive scan of the counts (shuffles within the wave,
-// the four wave totals through LDS) gives every lane its place in the round's LDS stage, the block
-// reserves the round's output slots with ONE global atomic, and the stage is copied out coalesced.
+// A block owns `per_block` consecutive items, one lane per line and round. A round's lanes hold
+// 0..8 pairs each: an exclusive scan of the counts (block_excl_count) gives every lane its place in
+// the round's LDS stage, the block reserves the round's output slots with ONE global atomic
+// (block_reserve), and the stage is copied out coalesced.
 __global__ __launch_bounds__(256) void k_line_keys(KeyLinesArgs A, int per_block) {
   __shared__ int64_t l_key[KL_STAGE];
   __shared__ int32_t l_line[KL_STAGE];
   __shared__ int s_wave[4];
   __shared__ int s_hit;
   __shared__ long long s_out;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const bool filter = A.tab.key != nullptr;
   if (threadIdx.x == 0) s_hit = 0;
   const int64_t base = (int64_t)blockIdx.x * per_block;
@@ -65,22 +60,9 @@ __global__ __launch_bounds__(256) void k_line_keys(KeyLinesArgs A, int per_block
     const int c = __popc(keep);
     if (i < A.n) A.hit[i] = c ? 1 : 0;
     hit_w += __popcll(__ballot(c != 0));
-    // exclusive scan of c over the round
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();                          // (also: the previous round's copy-out has read the stage)
-    int off = incl - c, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int t = s_wave[w];
-      off += w < wave ? t : 0;
-      total += t;
-    }
+    // exclusive scan of c over the round (its barrier also: the previous round's copy-out has read the stage)
+    int total;
+    int off = block_excl_count(c, s_wave, total);
     // stage: off + c <= total <= KL_STAGE
 #pragma unroll
     for (int j = 0; j < KEY_PER_LINE; ++j) {
@@ -90,17 +72,15 @@ __global__ __launch_bounds__(256) void k_line_keys(KeyLinesArgs A, int per_block
         ++off;
       }
     }
-    if (threadIdx.x == 0) s_out = total ? (long long)atomicAdd(A.cnt, (unsigned long long)total) : 0;
-    __syncthreads();
-    const int64_t o0 = s_out;
+    const int64_t o0 = block_reserve(A.cnt, total, &s_out);
     for (int j = threadIdx.x; j < total; j += KL_ROUND) {
       const int64_t o = o0 + j;
       if (o >= A.cap) break;                  // over capacity: counted above, the caller re-runs
       A.out_line[o] = l_line[j];
       A.out_key[o] = l_key[j];
     }
-    // (the next round's first barrier stands between this copy-out and its writes of the stage and
-    // of s_wave; s_out is written after that barrier)
+    // (the next round's scan barrier stands between this copy-out and its writes of the stage and
+    // of s_out; its write of s_wave comes after block_reserve's barrier of this round)
   }
   if (lane == 0 && hit_w) atomicAdd(&s_hit, hit_w);
   __syncthreads();
@@ -121,17 +101,11 @@ static void kl_check(const KeyLinesArgs& A, const char* who) {
 void line_keys_dev(const KeyLinesArgs& A, uint64_t stream, int per_block) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   kl_check(A, "line_keys_dev");
-  if (((uintptr_t)A.text & 15) != 0) throw std::runtime_error("line_keys_dev: text must be 16-byte aligned");
+  check_text_aligned(A.text, "line_keys_dev");
   if (A.n <= 0) return;
-  // lines per block: enough blocks to spread a small document over the CUs, 2048 for big ones
-  int per = per_block;
-  if (per <= 0) per = (int)std::min<int64_t>(KL_MAX_LINES, std::max<int64_t>(256, A.n / 2048));
-  per = (per + 255) / 256 * 256;
-  if (per > KL_MAX_LINES) throw std::runtime_error("line_keys_dev: per_block must be at most 2048");
-  const int64_t blocks = (A.n + per - 1) / per;
-  if (blocks > 0x7fffffffll) throw std::runtime_error("line_keys_dev: too many lines for one launch");
-  hipLaunchKernelGGL(k_line_keys, dim3((unsigned)blocks), dim3(256), 0, st, A, per);
-  LP_KCHECK(hipGetLastError());
+  const LineGeom g = line_geom(A.n, per_block, KL_MAX_LINES, "line_keys_dev");
+  hipLaunchKernelGGL(k_line_keys, dim3(g.blocks), dim3(256), 0, st, A, g.per);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void line_keys_host(const KeyLinesArgs& A) {

@@ -60,4 +60,45 @@ LP_HD int64_t gt_find(const GapTab& T, int64_t sig) {
   return -1;
 }
 
+#if defined(__HIPCC__)
+// The slot of key `k` in the key column `key` of a table of this layout (cap + 1 entries), claimed
+// if the key is new: 64-bit CAS on the key, linear probing, the side slot for the key that equals
+// the empty marker. The load before the CAS is only a shortcut: a key never changes once it is
+// written. -1 when every slot holds another key (the caller keeps the table at most half full, so
+// this is never reached; it is counted in *overflow all the same and nothing is lost silently). A
+// new slot is counted in *fresh (the block's LDS counter, or null: the caller knows the count):
+// one atomic on the table's `used` per new slot would put every claim of a launch on one address.
+__device__ __forceinline__ int64_t gt_claim(int64_t* key_col, int64_t cap, unsigned long long* overflow, int64_t k,
+                                            unsigned int* fresh) {
+  using ull = unsigned long long;
+  ull* key = reinterpret_cast<ull*>(key_col);
+  if (k == GT_EMPTY) {
+    if (atomicCAS(key + cap, 0ull, (ull)GT_EMPTY) == 0ull && fresh) atomicAdd(fresh, 1u);
+    return cap;
+  }
+  const int64_t mask = cap - 1;
+  int64_t s = (int64_t)(gt_hash(k) & (uint64_t)mask);
+  for (int64_t j = 0; j < cap; ++j) {
+    ull v = __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v == (ull)GT_EMPTY) {
+      v = atomicCAS(key + s, (ull)GT_EMPTY, (ull)k);
+      if (v == (ull)GT_EMPTY) {
+        if (fresh) atomicAdd(fresh, 1u);
+        return s;
+      }
+    }
+    if (v == (ull)k) return s;
+    s = (s + 1) & mask;
+  }
+  atomicAdd(overflow, 1ull);
+  return -1;
+}
+
+// on a table struct with the columns key, used and cap (GapTab, cell_table.h CellTab)
+template <class Tab>
+__device__ __forceinline__ int64_t gt_claim(const Tab& T, int64_t k, unsigned int* fresh) {
+  return gt_claim(T.key, T.cap, T.used + 1, k, fresh);
+}
+#endif
+
 }  // namespace lp

@@ -17,50 +17,15 @@
 
 #include "gap_table.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 
 namespace lp {
 
-#define LP_TCHECK(x)                                                                                            \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
-
 namespace {
 
 using ull = unsigned long long;
-
-// the slot of `sig`, claimed if the signature is new (64-bit CAS on the key, linear probing). The
-// load before the CAS is only a shortcut: a key never changes once it is written. -1 when every
-// slot holds another key (the caller keeps the table at most half full, so this is never reached;
-// it is counted in used[1] all the same and the pair is not lost silently). A new slot is counted
-// in *fresh (the block's LDS counter, or null: the caller knows the count): one atomic on the
-// table's `used` per new slot would put every claim of a launch on one address.
-__device__ __forceinline__ int64_t gt_claim(const GapTab& T, int64_t sig, unsigned int* fresh) {
-  ull* key = reinterpret_cast<ull*>(T.key);
-  if (sig == GT_EMPTY) {
-    if (atomicCAS(key + T.cap, 0ull, (ull)GT_EMPTY) == 0ull && fresh) atomicAdd(fresh, 1u);
-    return T.cap;
-  }
-  const int64_t mask = T.cap - 1;
-  int64_t s = (int64_t)(gt_hash(sig) & (uint64_t)mask);
-  for (int64_t k = 0; k < T.cap; ++k) {
-    ull v = __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (v == (ull)GT_EMPTY) {
-      v = atomicCAS(key + s, (ull)GT_EMPTY, (ull)sig);
-      if (v == (ull)GT_EMPTY) {
-        if (fresh) atomicAdd(fresh, 1u);
-        return s;
-      }
-    }
-    if (v == (ull)sig) return s;
-    s = (s + 1) & mask;
-  }
-  atomicAdd(T.used + 1, 1ull);
-  return -1;
-}
 
 // `cnt` pairs of document `doc` with smallest ordinal `ord` into slot s. The old value of the
 // atomicMax tells the first arrival of a document apart (one document per launch, document
@@ -131,25 +96,18 @@ __global__ __launch_bounds__(256) void k_gap_fold(GapTab T, const int64_t* __res
   if (threadIdx.x == 0 && s_fresh) atomicAdd(T.used, (ull)s_fresh);
 }
 
-// one lane per pair; the winners of a wave reserve their output slots with one atomic (k_gap_sig)
+// one lane per pair; the winners of a wave reserve their output slots with one atomic (wave_list_append)
 __global__ __launch_bounds__(256) void k_gap_winners(GapTab T, const int64_t* __restrict__ sig,
                                                      const int64_t* __restrict__ ord, int64_t n,
                                                      int64_t* __restrict__ out, ull* cnt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   bool win = false;
   if (i < n) {
     const int64_t s = gt_find(T, sig[i]);
     win = s >= 0 && T.first[s] == ord[i];
   }
-  const ull m = __ballot(win);
-  if (m) {                                   // wave-uniform
-    ull o0 = 0;
-    if (lane == 0) o0 = atomicAdd(cnt, (ull)__popcll(m));
-    o0 = __shfl(o0, 0, 64);
-    const int64_t o = (int64_t)o0 + __popcll(m & ((1ull << lane) - 1ull));
-    if (win && o < n) out[o] = i;            // (at most n winners: every pair is appended once)
-  }
+  const int64_t o = (int64_t)wave_list_append(__ballot(win), cnt);
+  if (win && o < n) out[o] = i;              // (at most n winners: every pair is appended once)
 }
 
 // one lane per slot, the side slot included
@@ -157,21 +115,14 @@ __global__ __launch_bounds__(256) void k_gap_rows(GapTab T, int64_t* __restrict_
                                                   int64_t* __restrict__ o_first, int32_t* __restrict__ o_docs,
                                                   int32_t* __restrict__ o_last, int64_t out_cap, ull* cnt) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   const bool occ = s <= T.cap && gt_occupied(T, s);
-  const ull m = __ballot(occ);
-  if (m) {
-    ull o0 = 0;
-    if (lane == 0) o0 = atomicAdd(cnt, (ull)__popcll(m));
-    o0 = __shfl(o0, 0, 64);
-    const int64_t o = (int64_t)o0 + __popcll(m & ((1ull << lane) - 1ull));
-    if (occ && o < out_cap) {                // over capacity: counted, the caller sees cnt > out_cap
-      o_sig[o] = s < T.cap ? T.key[s] : GT_EMPTY;
-      o_count[o] = (int64_t)T.count[s];
-      o_first[o] = T.first[s];
-      o_docs[o] = T.docs[s];
-      o_last[o] = T.last_doc[s];
-    }
+  const int64_t o = (int64_t)wave_list_append(__ballot(occ), cnt);
+  if (occ && o < out_cap) {                  // over capacity: counted, the caller sees cnt > out_cap
+    o_sig[o] = s < T.cap ? T.key[s] : GT_EMPTY;
+    o_count[o] = (int64_t)T.count[s];
+    o_first[o] = T.first[s];
+    o_docs[o] = T.docs[s];
+    o_last[o] = T.last_doc[s];
   }
 }
 
@@ -198,12 +149,6 @@ static void gt_check(const GapTab& T, const char* who) {
     throw std::runtime_error(std::string(who) + ": missing table column");
 }
 
-static unsigned gt_blocks(int64_t n, int per, const char* who) {
-  const int64_t b = (n + per - 1) / per;
-  if (b > 0x7fffffffll) throw std::runtime_error(std::string(who) + ": too many items for one launch");
-  return (unsigned)b;
-}
-
 void gap_fold_dev(const GapTab& T, const int64_t* sig, const int64_t* ord, int64_t n, int doc, uint64_t stream,
                   int tile) {
   gt_check(T, "gap_fold_dev");
@@ -213,8 +158,8 @@ void gap_fold_dev(const GapTab& T, const int64_t* sig, const int64_t* ord, int64
   if (tile <= 0) tile = (int)std::min<int64_t>(GT_TILE, std::max<int64_t>(256, (n / GT_BLOCKS + 255) / 256 * 256));
   if (tile < 256 || tile > GT_TILE || tile % 256) throw std::runtime_error("gap_fold_dev: tile must be 256..2048, a multiple of 256");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_gap_fold, dim3(gt_blocks(n, tile, "gap_fold_dev")), dim3(256), 0, st, T, sig, ord, n, doc, tile);
-  LP_TCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gap_fold, dim3(launch_blocks(n, tile, "gap_fold_dev")), dim3(256), 0, st, T, sig, ord, n, doc, tile);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void gap_winners_dev(const GapTab& T, const int64_t* sig, const int64_t* ord, int64_t n, int64_t* out,
@@ -222,25 +167,25 @@ void gap_winners_dev(const GapTab& T, const int64_t* sig, const int64_t* ord, in
   gt_check(T, "gap_winners_dev");
   if (n <= 0) return;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_gap_winners, dim3(gt_blocks(n, 256, "gap_winners_dev")), dim3(256), 0, st, T, sig, ord, n, out, cnt);
-  LP_TCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gap_winners, dim3(launch_blocks(n, 256, "gap_winners_dev")), dim3(256), 0, st, T, sig, ord, n, out, cnt);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void gap_rows_dev(const GapTab& T, const GapRows& R, int64_t out_cap, unsigned long long* cnt, uint64_t stream) {
   gt_check(T, "gap_rows_dev");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_gap_rows, dim3(gt_blocks(T.cap + 1, 256, "gap_rows_dev")), dim3(256), 0, st, T, R.sig, R.count,
+  hipLaunchKernelGGL(k_gap_rows, dim3(launch_blocks(T.cap + 1, 256, "gap_rows_dev")), dim3(256), 0, st, T, R.sig, R.count,
                      R.first, R.docs, R.last_doc, out_cap, cnt);
-  LP_TCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void gap_reinsert_dev(const GapTab& T, const GapRows& R, int64_t n, uint64_t stream) {
   gt_check(T, "gap_reinsert_dev");
   if (n <= 0) return;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_gap_reinsert, dim3(gt_blocks(n, 256, "gap_reinsert_dev")), dim3(256), 0, st, T, R.sig, R.count,
+  hipLaunchKernelGGL(k_gap_reinsert, dim3(launch_blocks(n, 256, "gap_reinsert_dev")), dim3(256), 0, st, T, R.sig, R.count,
                      R.first, R.docs, R.last_doc, n);
-  LP_TCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 // ---- host twins: the same table layout, one thread (the table work of a chunk is small next to

@@ -14,22 +14,17 @@
 
 #include "gaps_core.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 
 namespace lp {
 
-#define LP_GCHECK(x)                                                                                            \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
-
 // A block owns `per_block` consecutive lines (k_feat_cov's structure). Selected lines are a few
 // percent of all lines and cost up to 1 KiB of dependent work each, so one lane per line would idle
-// most of every wave: the block compacts its selected lines into an LDS list (ballot + prefix, one
-// LDS atomic per wave) and its lanes then take lines from the list. The block reserves its output
-// slots with ONE global atomic -- the list's length is known before any line is signed.
+// most of every wave: the block compacts its selected lines into an LDS list (wave_list_append) and
+// its lanes then take lines from the list. The block reserves its output slots with ONE global
+// atomic (block_reserve) -- the list's length is known before any line is signed.
 constexpr int GS_MAX_LINES = 4096;   // lines per block (uint16 list entries)
 
 __global__ __launch_bounds__(256) void k_gap_sig(GapSigArgs A, int per_block) {
@@ -52,25 +47,15 @@ __global__ __launch_bounds__(256) void k_gap_sig(GapSigArgs A, int per_block) {
       cand = gap_candidate(A.feat[x]);
       pick = cand && !(A.cov && A.cov[x]);
     }
-    const unsigned long long mc = __ballot(cand), mp = __ballot(pick);
-    cand_w += __popcll(mc);
-    const int np = __popcll(mp);
-    if (np) {                                // wave-uniform
-      int slot = 0;
-      if (lane == 0) slot = atomicAdd(&s_n, np);
-      slot = __shfl(slot, 0, 64);
-      if (pick) list[slot + __popcll(mp & ((1ull << lane) - 1ull))] = (uint16_t)k;
-    }
+    cand_w += __popcll(__ballot(cand));
+    const int j = wave_list_append(__ballot(pick), &s_n);
+    if (pick) list[j] = (uint16_t)k;
   }
   if (lane == 0 && cand_w) atomicAdd(&s_cand, cand_w);
   __syncthreads();
   const int m = s_n;                         // <= per_block <= GS_MAX_LINES
-  if (threadIdx.x == 0) {
-    if (s_cand) atomicAdd(A.cnt, (unsigned long long)s_cand);
-    s_out = m ? (long long)atomicAdd(A.cnt + 1, (unsigned long long)m) : 0;
-  }
-  __syncthreads();
-  const int64_t o0 = s_out;
+  if (threadIdx.x == 0 && s_cand) atomicAdd(A.cnt, (unsigned long long)s_cand);
+  const int64_t o0 = block_reserve(A.cnt + 1, m, &s_out);
   for (int j = threadIdx.x; j < m; j += (int)blockDim.x) {
     const int64_t o = o0 + j;
     if (o >= A.cap) break;                   // over capacity: counted above, the caller re-runs
@@ -95,21 +80,20 @@ __global__ __launch_bounds__(256) void k_gap_sig_list(GapSigArgs A, int64_t n) {
 
 void gap_sig_dev(const GapSigArgs& A, uint64_t stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (((uintptr_t)A.text & 15) != 0) throw std::runtime_error("gap_sig_dev: text must be 16-byte aligned");
+  check_text_aligned(A.text, "gap_sig_dev");
   if (A.sel || A.all) {
     const int64_t n = A.sel ? A.nsel : A.L;
     if (n <= 0) return;
     hipLaunchKernelGGL(k_gap_sig_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n);
-    LP_GCHECK(hipGetLastError());
+    LP_HIP_CHECK(hipGetLastError());
     return;
   }
   if (A.L <= 0) return;
   if (!A.feat) throw std::runtime_error("gap_sig_dev: the self-selecting form needs the features of every line");
-  // lines per block: enough blocks to spread a small document over the CUs, 4096 for big ones
-  int per = (int)std::min<int64_t>(GS_MAX_LINES, std::max<int64_t>(256, A.L / 1024));
-  per = (per + 255) / 256 * 256;
-  hipLaunchKernelGGL(k_gap_sig, dim3((unsigned)((A.L + per - 1) / per)), dim3(256), 0, st, A, per);
-  LP_GCHECK(hipGetLastError());
+  // lines per block: L / 1024 for a small document, 4096 for big ones
+  const LineGeom g = line_geom(A.L, 0, GS_MAX_LINES, "gap_sig_dev", 1024);
+  hipLaunchKernelGGL(k_gap_sig, dim3(g.blocks), dim3(256), 0, st, A, g.per);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void gap_sig_host(const GapSigArgs& A) {

@@ -13,16 +13,11 @@
 
 #include "gaps_core.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 
 namespace lp {
-
-#define LP_LCHECK(x)                                                                                            \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
 
 constexpr int LD_MAX_LINES = 2048;   // lines per block: 10 bytes of LDS each
 constexpr int LD_MAX_WINDOW = 4096;
@@ -39,16 +34,15 @@ LP_HD bool lead_before_event(const int32_t* __restrict__ ev, int64_t ne, int64_t
   return lo < ne && (int64_t)ev[lo] <= x + (int64_t)W;
 }
 
-// A block owns `per_block` consecutive lines (k_novel_sig's structure), one lane per line and
-// round. The lead-up lines of the block are compacted into an LDS list (ballot + prefix, one LDS
-// atomic per wave and round) with their signatures, and the block reserves its output slots with
-// ONE global atomic once the list is complete.
+// A block owns `per_block` consecutive lines, one lane per line and round. The lead-up lines of the
+// block are compacted into an LDS list (wave_list_append: one LDS atomic per wave and round) with
+// their signatures, and the block reserves its output slots with ONE global atomic (block_reserve)
+// once the list is complete.
 __global__ __launch_bounds__(256) void k_lead_sig(LeadSigArgs A, int per_block) {
   __shared__ int64_t l_sig[LD_MAX_LINES];
   __shared__ uint16_t l_k[LD_MAX_LINES];      // block-relative numbers of the lead-up lines
   __shared__ int s_n;
   __shared__ long long s_out;
-  const int lane = threadIdx.x & 63;
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
   const int64_t base = (int64_t)blockIdx.x * per_block;
@@ -63,24 +57,15 @@ __global__ __launch_bounds__(256) void k_lead_sig(LeadSigArgs A, int per_block) 
       A.sig[x] = sig;
       A.lead[x] = lead ? 1 : 0;
     }
-    const unsigned long long ml = __ballot(lead);
-    const int nn = __popcll(ml);
-    if (nn) {                                // wave-uniform
-      int slot = 0;
-      if (lane == 0) slot = atomicAdd(&s_n, nn);
-      slot = __shfl(slot, 0, 64);
-      if (lead) {
-        const int j = slot + __popcll(ml & ((1ull << lane) - 1ull));   // < per_block <= LD_MAX_LINES
-        l_sig[j] = sig;
-        l_k[j] = (uint16_t)k;
-      }
+    const int j = wave_list_append(__ballot(lead), &s_n);   // < per_block <= LD_MAX_LINES
+    if (lead) {
+      l_sig[j] = sig;
+      l_k[j] = (uint16_t)k;
     }
   }
   __syncthreads();
   const int m = s_n;                         // <= per_block <= LD_MAX_LINES
-  if (threadIdx.x == 0) s_out = m ? (long long)atomicAdd(A.cnt, (unsigned long long)m) : 0;
-  __syncthreads();
-  const int64_t o0 = s_out;
+  const int64_t o0 = block_reserve(A.cnt, m, &s_out);
   for (int j = threadIdx.x; j < m; j += (int)blockDim.x) {
     const int64_t o = o0 + j;
     if (o >= A.cap) break;                   // over capacity: counted above, the caller re-runs
@@ -99,16 +84,11 @@ static void ld_check(const LeadSigArgs& A, const char* who) {
 void lead_sig_dev(const LeadSigArgs& A, uint64_t stream, int per_block) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   ld_check(A, "lead_sig_dev");
-  if (((uintptr_t)A.text & 15) != 0) throw std::runtime_error("lead_sig_dev: text must be 16-byte aligned");
+  check_text_aligned(A.text, "lead_sig_dev");
   if (A.L <= 0) return;
-  // lines per block: enough blocks to spread a small document over the CUs, 2048 for big ones
-  int per = per_block;
-  if (per <= 0) per = (int)std::min<int64_t>(LD_MAX_LINES, std::max<int64_t>(256, A.L / 2048));
-  per = (per + 255) / 256 * 256;
-  if (per > LD_MAX_LINES) throw std::runtime_error("lead_sig_dev: per_block must be at most 2048");
-  const int64_t blocks = (A.L + per - 1) / per;
-  hipLaunchKernelGGL(k_lead_sig, dim3((unsigned)blocks), dim3(256), 0, st, A, per);
-  LP_LCHECK(hipGetLastError());
+  const LineGeom g = line_geom(A.L, per_block, LD_MAX_LINES, "lead_sig_dev");
+  hipLaunchKernelGGL(k_lead_sig, dim3(g.blocks), dim3(256), 0, st, A, g.per);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void lead_sig_host(const LeadSigArgs& A) {

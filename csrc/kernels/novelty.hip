@@ -15,26 +15,21 @@
 #include "gap_table.h"
 #include "gaps_core.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 
 namespace lp {
 
-#define LP_NCHECK(x)                                                                                            \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
-
 // flag bits of a novel line
 constexpr uint8_t NV_CAND = 1;    // gap_candidate(feat[x])
 constexpr uint8_t NV_EVENT = 2;   // an event lies on the line
 
-// A block owns `per_block` consecutive lines (k_gap_sig's structure), one lane per line and round:
-// every line is signed, so there is no selection to balance first. The novel lines of the block
-// are compacted into an LDS list (ballot + prefix, one LDS atomic per wave and round) WITH their
-// signatures -- a signature costs up to 1 KiB of dependent work and is not computed twice -- and
-// the block reserves its output slots with ONE global atomic once the list is complete.
+// A block owns `per_block` consecutive lines, one lane per line and round: every line is signed,
+// so there is no selection to balance first. The novel lines of the block are compacted into an
+// LDS list (wave_list_append: one LDS atomic per wave and round) WITH their signatures -- a
+// signature costs up to 1 KiB of dependent work and is not computed twice -- and the block
+// reserves its output slots with ONE global atomic (block_reserve) once the list is complete.
 constexpr int NV_MAX_LINES = 2048;   // lines per block: 11 bytes of LDS each
 
 __global__ __launch_bounds__(256) void k_novel_sig(NovelSigArgs A, int per_block) {
@@ -67,17 +62,11 @@ __global__ __launch_bounds__(256) void k_novel_sig(NovelSigArgs A, int per_block
     const unsigned long long mc = __ballot(cand), mn = __ballot(novel);
     cand_w += __popcll(mc);
     ncand_w += __popcll(mc & mn);
-    const int nn = __popcll(mn);
-    if (nn) {                                // wave-uniform
-      int slot = 0;
-      if (lane == 0) slot = atomicAdd(&s_n, nn);
-      slot = __shfl(slot, 0, 64);
-      if (novel) {
-        const int j = slot + __popcll(mn & ((1ull << lane) - 1ull));   // < per_block <= NV_MAX_LINES
-        l_sig[j] = sig;
-        l_k[j] = (uint16_t)k;
-        l_flag[j] = flag;
-      }
+    const int j = wave_list_append(mn, &s_n);   // < per_block <= NV_MAX_LINES
+    if (novel) {
+      l_sig[j] = sig;
+      l_k[j] = (uint16_t)k;
+      l_flag[j] = flag;
     }
   }
   if (lane == 0) {
@@ -89,10 +78,8 @@ __global__ __launch_bounds__(256) void k_novel_sig(NovelSigArgs A, int per_block
   if (threadIdx.x == 0) {
     if (s_cand) atomicAdd(A.cnt, (unsigned long long)s_cand);
     if (s_ncand) atomicAdd(A.cnt + 2, (unsigned long long)s_ncand);
-    s_out = m ? (long long)atomicAdd(A.cnt + 1, (unsigned long long)m) : 0;
   }
-  __syncthreads();
-  const int64_t o0 = s_out;
+  const int64_t o0 = block_reserve(A.cnt + 1, m, &s_out);
   for (int j = threadIdx.x; j < m; j += (int)blockDim.x) {
     const int64_t o = o0 + j;
     if (o >= A.cap) break;                   // over capacity: counted above, the caller re-runs
@@ -117,27 +104,20 @@ static void nv_check_tab(const GapTab& T, const char* who) {
 void novel_sig_dev(const NovelSigArgs& A, uint64_t stream, int per_block) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   nv_check_tab(A.tab, "novel_sig_dev");
-  if (((uintptr_t)A.text & 15) != 0) throw std::runtime_error("novel_sig_dev: text must be 16-byte aligned");
+  check_text_aligned(A.text, "novel_sig_dev");
   if (A.L <= 0) return;
-  // lines per block: enough blocks to spread a small document over the CUs, 2048 for big ones
-  int per = per_block;
-  if (per <= 0) per = (int)std::min<int64_t>(NV_MAX_LINES, std::max<int64_t>(256, A.L / 2048));
-  per = (per + 255) / 256 * 256;
-  if (per > NV_MAX_LINES) throw std::runtime_error("novel_sig_dev: per_block must be at most 2048");
-  const int64_t blocks = (A.L + per - 1) / per;
-  if (blocks > 0x7fffffffll) throw std::runtime_error("novel_sig_dev: too many lines for one launch");
-  hipLaunchKernelGGL(k_novel_sig, dim3((unsigned)blocks), dim3(256), 0, st, A, per);
-  LP_NCHECK(hipGetLastError());
+  const LineGeom g = line_geom(A.L, per_block, NV_MAX_LINES, "novel_sig_dev");
+  hipLaunchKernelGGL(k_novel_sig, dim3(g.blocks), dim3(256), 0, st, A, g.per);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void gap_contains_dev(const GapTab& T, const int64_t* sig, int64_t n, uint8_t* out, uint64_t stream) {
   nv_check_tab(T, "gap_contains_dev");
   if (n <= 0) return;
-  const int64_t blocks = (n + 255) / 256;
-  if (blocks > 0x7fffffffll) throw std::runtime_error("gap_contains_dev: too many signatures for one launch");
+  const unsigned blocks = launch_blocks(n, 256, "gap_contains_dev", "signatures");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_gap_contains, dim3((unsigned)blocks), dim3(256), 0, st, T, sig, n, out);
-  LP_NCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_gap_contains, dim3(blocks), dim3(256), 0, st, T, sig, n, out);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void novel_sig_host(const NovelSigArgs& A) {

@@ -22,17 +22,12 @@
 #include <string>
 
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 #include "ts_core.h"
 
 namespace lp {
-
-#define LP_PSCHECK(x)                                                                                           \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
 
 namespace {
 using ull = unsigned long long;
@@ -71,27 +66,10 @@ __device__ __forceinline__ PsPair ps_lane(const int64_t* __restrict__ ts, int64_
   return p;
 }
 
-// inclusive scan of the lanes' pairs over the block (Hillis-Steele in LDS, tf_block_scan's form);
-// returns the lane's EXCLUSIVE pair, and the block's total in `total`
+// the lane's EXCLUSIVE pair of the scan over the block, and the block's total in `total`
 __device__ __forceinline__ PsPair ps_block_scan(PsPair mine, PsPair* s, PsPair& total) {
-  const int t = threadIdx.x;
-  s[t] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    PsPair x = s[t];
-    if (t >= d) x = ps_join(s[t - d], x);
-    __syncthreads();
-    s[t] = x;
-    __syncthreads();
-  }
-  total = s[255];
-  return t ? s[t - 1] : PsPair{TS_NONE, -1};
-}
-
-__device__ __forceinline__ unsigned int ps_wave_sum(unsigned int x) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
+  return block_scan_excl(mine, PsPair{TS_NONE, -1}, s, total,
+                         [](const PsPair& a, const PsPair& b) { return ps_join(a, b); });
 }
 
 __global__ __launch_bounds__(256) void k_ps_tiles(const int64_t* __restrict__ ts, int64_t L, int64_t line_base,
@@ -117,7 +95,7 @@ __global__ __launch_bounds__(256) void k_ps_tiles(const int64_t* __restrict__ ts
     else n += ps_is_pause(ps_step(p.ts, v[j]), min_ms) ? 1u : 0u;
     p = PsPair{v[j], 0};
   }
-  n = ps_wave_sum(n);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(&s_cnt, n);
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -156,16 +134,8 @@ __global__ __launch_bounds__(256) void k_ps_prefix(PauseArgs A, int64_t* __restr
     t_line[k] = p.line;
     p = ps_join(p, own);
   }
-  s_sum[t] = c;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    long long x = s_sum[t];
-    if (t >= d) x += s_sum[t - d];
-    __syncthreads();
-    s_sum[t] = x;
-    __syncthreads();
-  }
-  long long off = t ? s_sum[t - 1] : 0;
+  long long sum;
+  long long off = block_scan_excl(c, 0ll, s_sum, sum, [](long long x, long long y) { return x + y; });
   for (int64_t k = a; k < b; ++k) {
     const long long n = t_cnt[k];
     t_cnt[k] = off;
@@ -173,7 +143,7 @@ __global__ __launch_bounds__(256) void k_ps_prefix(PauseArgs A, int64_t* __restr
   }
   if (t == 255) {
     total = ps_join(carry, total);
-    A.head[0] = s_sum[255];
+    A.head[0] = sum;
     A.head[1] = total.ts;
     A.head[2] = total.ts != TS_NONE ? total.line : -1;
     A.head[3] = total.ts != TS_NONE ? ps_from_sig(A, total.line) : 0;
@@ -189,7 +159,6 @@ __global__ __launch_bounds__(256) void k_ps_emit(PauseArgs A, const int64_t* __r
   __shared__ unsigned int s_stamped, s_back;
   __shared__ ull s_paused;
   __shared__ long long s_min, s_max;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x < PS_BUCKETS) s_hist[threadIdx.x] = 0u;
   if (threadIdx.x == 0) {
     s_stamped = s_back = 0u;
@@ -237,36 +206,24 @@ __global__ __launch_bounds__(256) void k_ps_emit(PauseArgs A, const int64_t* __r
     q = PsPair{v[j], A.line_base + i0 + j};
   }
   if (hn) atomicAdd(&s_hist[hb], hn);
-  // exclusive scan of the lanes' pause counts over the block (k_cell_rows)
-  int incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int x = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += x;
-  }
-  if (lane == 63) s_wave[wave] = incl;
   // the statistics: per wave in registers, per block in LDS, then one set of global atomics
-  stamped = ps_wave_sum(stamped);
-  back = ps_wave_sum(back);
-#pragma unroll
-  for (int d = 32; d; d >>= 1) {
-    paused += (ull)__shfl_xor((long long)paused, d, 64);
-    const long long a = __shfl_xor(mn, d, 64), b = __shfl_xor(mx, d, 64);
-    mn = a < mn ? a : mn;
-    mx = b > mx ? b : mx;
-  }
-  if (lane == 0 && stamped) {
+  stamped = wave_sum(stamped);
+  back = wave_sum(back);
+  paused = wave_reduce(paused, [](ull a, ull b) { return a + b; });
+  mn = wave_reduce(mn, [](long long a, long long b) { return b < a ? b : a; });
+  mx = wave_reduce(mx, [](long long a, long long b) { return b > a ? b : a; });
+  if ((threadIdx.x & 63) == 0 && stamped) {
     atomicAdd(&s_stamped, stamped);
     if (back) atomicAdd(&s_back, back);
     if (paused) atomicAdd(&s_paused, paused);
     atomicMin(&s_min, mn);
     atomicMax(&s_max, mx);
   }
-  __syncthreads();
+  // the lanes' places among the block's pause rows (the scan's barrier orders the LDS statistics too)
+  int pauses;
+  const int off = block_excl_count(c, s_wave, pauses);
   if (c) {
-    int64_t o = t_off[blockIdx.x] + (incl - c);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) o += w < wave ? s_wave[w] : 0;
+    int64_t o = t_off[blockIdx.x] + off;
     q = p;
 #pragma unroll
     for (int j = 0; j < PS_PER_LANE; ++j) {
@@ -328,9 +285,9 @@ void pause_count_dev(const PauseArgs& A, uint64_t stream) {
   int64_t *t_first = A.tmp, *t_last = A.tmp + nt, *t_line = A.tmp + 2 * nt, *t_cnt = A.tmp + 3 * nt;
   hipLaunchKernelGGL(k_ps_tiles, dim3((unsigned)nt), dim3(256), 0, st, A.ts, A.L, A.line_base, A.min_ms, t_first, t_last,
                      t_line, t_cnt);
-  LP_PSCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_ps_prefix, dim3(1), dim3(256), 0, st, A, t_first, t_last, t_line, t_cnt, nt);
-  LP_PSCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void pause_emit_dev(const PauseArgs& A, uint64_t stream) {
@@ -340,7 +297,7 @@ void pause_emit_dev(const PauseArgs& A, uint64_t stream) {
   const int64_t nt = ps_tiles_of(A.L);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_ps_emit, dim3((unsigned)nt), dim3(256), 0, st, A, A.tmp + nt, A.tmp + 2 * nt, A.tmp + 3 * nt);
-  LP_PSCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 // ---- host twins: one walk in line order

@@ -12,17 +12,12 @@
 
 #include "gaps_core.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 #include "ts_core.h"
 
 namespace lp {
-
-#define LP_TLCHECK(x)                                                                                           \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
 
 // one lane per line (k_gap_sig_list's form): a stamp at the head of the line settles within the
 // lane's first two or three 16-byte loads
@@ -37,11 +32,11 @@ __global__ __launch_bounds__(256) void k_ts_parse(const uint8_t* __restrict__ te
 void ts_parse_dev(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, int64_t* out,
                   uint64_t stream) {
   if (L <= 0) return;
-  if (((uintptr_t)text & 15) != 0) throw std::runtime_error("ts_parse_dev: text must be 16-byte aligned");
-  if ((L + 255) / 256 > 0x7fffffffll) throw std::runtime_error("ts_parse_dev: too many lines for one launch");
+  check_text_aligned(text, "ts_parse_dev");
+  const unsigned blocks = launch_blocks(L, 256, "ts_parse_dev", "lines");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_ts_parse, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, text, tbytes, ls, ll, L, out);
-  LP_TLCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_ts_parse, dim3(blocks), dim3(256), 0, st, text, tbytes, ls, ll, L, out);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void ts_parse_host(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, int64_t* out) {
@@ -79,21 +74,10 @@ __device__ __forceinline__ TfPair tf_lane(const int64_t* __restrict__ ts, int64_
   return p;
 }
 
-// inclusive scan of the lanes' pairs over the block (Hillis-Steele in LDS); returns the lane's
-// EXCLUSIVE pair, and the block's total in `total`
+// the lane's EXCLUSIVE pair of the scan over the block, and the block's total in `total`
 __device__ __forceinline__ TfPair tf_block_scan(TfPair mine, TfPair* s, TfPair& total) {
-  const int t = threadIdx.x;
-  s[t] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    TfPair x = s[t];
-    if (t >= d) x = tf_join(s[t - d], x);
-    __syncthreads();
-    s[t] = x;
-    __syncthreads();
-  }
-  total = s[255];
-  return t ? s[t - 1] : TfPair{TS_NONE, TS_NONE};
+  return block_scan_excl(mine, TfPair{TS_NONE, TS_NONE}, s, total,
+                         [](const TfPair& a, const TfPair& b) { return tf_join(a, b); });
 }
 
 __global__ __launch_bounds__(256) void k_tl_tiles(const int64_t* __restrict__ ts, int64_t L,
@@ -154,18 +138,17 @@ __global__ __launch_bounds__(256) void k_tl_fill(const int64_t* __restrict__ ts,
 void tl_fill_dev(const int64_t* ts, int64_t L, int64_t carry_last, int64_t carry_top, int64_t* eff,
                  unsigned long long* ooo, int64_t* tmp, uint64_t stream) {
   if (L <= 0) return;
-  const int64_t nt = (L + TF_TILE - 1) / TF_TILE;
-  if (nt > 0x7fffffffll) throw std::runtime_error("tl_fill_dev: too many lines for one launch");
+  const int64_t nt = launch_blocks(L, TF_TILE, "tl_fill_dev", "lines");
   if (!ts || !eff || !ooo || !tmp) throw std::runtime_error("tl_fill_dev: missing buffer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int64_t* t_last = tmp;
   int64_t* t_top = tmp + nt;
   hipLaunchKernelGGL(k_tl_tiles, dim3((unsigned)nt), dim3(256), 0, st, ts, L, t_last, t_top);
-  LP_TLCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_tl_prefix, dim3(1), dim3(256), 0, st, t_last, t_top, nt, carry_last, carry_top);
-  LP_TLCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_tl_fill, dim3((unsigned)nt), dim3(256), 0, st, ts, L, t_last, t_top, eff, ooo);
-  LP_TLCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 int64_t tl_fill_tmp_words(int64_t L) { return 2 * ((std::max<int64_t>(L, 0) + TF_TILE - 1) / TF_TILE); }
@@ -277,11 +260,10 @@ void tl_hist_dev(const TlHistArgs& A, uint64_t stream) {
     throw std::runtime_error("tl_hist_dev: too many severities for the block table");
   int slots = TL_LDS_SLOTS;
   while ((int64_t)slots * (C + 1) * 4 > TL_LDS_BYTES) slots >>= 1;      // (a power of two, >= 1)
-  const int64_t blocks = (n + TL_TILE - 1) / TL_TILE;
-  if (blocks > 0x7fffffffll) throw std::runtime_error("tl_hist_dev: too many items for one launch");
+  const unsigned blocks = launch_blocks(n, TL_TILE, "tl_hist_dev");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_tl_hist, dim3((unsigned)blocks), dim3(256), (size_t)slots * (C + 1) * 4, st, A, slots);
-  LP_TLCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_tl_hist, dim3(blocks), dim3(256), (size_t)slots * (C + 1) * 4, st, A, slots);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void tl_hist_host(const TlHistArgs& A) {

@@ -15,17 +15,12 @@
 #include <string>
 
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 #include "trace_core.h"
 
 namespace lp {
-
-#define LP_TRCHECK(x)                                                                                           \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
 
 constexpr int TR_PER_LANE = 4;                       // consecutive lines of one lane
 constexpr int TR_TILE_LINES = 256 * TR_PER_LANE;     // lines of one block
@@ -54,21 +49,10 @@ __device__ __forceinline__ TrAgg tr_lane(const TraceRunArgs& A, int64_t i0) {
   return p;
 }
 
-// inclusive scan of the lanes' aggregates over the block (Hillis-Steele in LDS); returns the
-// lane's EXCLUSIVE aggregate, and the block's total in `total`
+// the lane's EXCLUSIVE aggregate of the scan over the block, and the block's total in `total`
 __device__ __forceinline__ TrAgg tr_block_scan(const TrAgg& mine, TrAgg* s, TrAgg& total) {
-  const int t = threadIdx.x;
-  s[t] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    TrAgg x = s[t];
-    if (t >= d) x = tr_combine(s[t - d], x);
-    __syncthreads();
-    s[t] = x;
-    __syncthreads();
-  }
-  total = s[255];
-  return t ? s[t - 1] : tr_identity();
+  return block_scan_excl(mine, tr_identity(), s, total,
+                         [](const TrAgg& a, const TrAgg& b) { return tr_combine(a, b); });
 }
 
 __global__ __launch_bounds__(256) void k_tr_tiles(TraceRunArgs A, TrAgg* __restrict__ tiles) {
@@ -158,12 +142,12 @@ __device__ __forceinline__ unsigned tr_walk(const TraceRunArgs& A, TrAgg p, int6
 }
 
 // The lanes count their rows first; the block reserves its output slots with ONE global atomic
-// (k_novel_sig's scheme: thousands of returning atomics on one address would serialise), and the
-// lanes walk their lines a second time to write.
+// (block_reserve: thousands of returning atomics on one address would serialise), and the lanes
+// walk their lines a second time to write.
 __global__ __launch_bounds__(256) void k_tr_emit(TraceRunArgs A, const TrAgg* __restrict__ tiles) {
   __shared__ TrAgg s[256];
   __shared__ unsigned int s_n;
-  __shared__ unsigned long long s_base;
+  __shared__ long long s_base;
   if (threadIdx.x == 0) s_n = 0u;
   const int64_t i0 = (int64_t)blockIdx.x * TR_TILE_LINES + (int64_t)threadIdx.x * TR_PER_LANE;
   TrAgg total;
@@ -172,9 +156,7 @@ __global__ __launch_bounds__(256) void k_tr_emit(TraceRunArgs A, const TrAgg* __
   const unsigned mine = tr_walk<false>(A, p, i0, 0);
   const unsigned at = mine ? atomicAdd(&s_n, mine) : 0u;
   __syncthreads();
-  if (threadIdx.x == 0) s_base = s_n ? atomicAdd(A.cnt, (unsigned long long)s_n) : 0ull;
-  __syncthreads();
-  tr_walk<true>(A, p, i0, (int64_t)s_base + at);
+  tr_walk<true>(A, p, i0, block_reserve(A.cnt, (int)s_n, &s_base) + at);
 }
 
 static void tr_check(const TraceRunArgs& A, const char* who) {
@@ -187,11 +169,11 @@ static void tr_check(const TraceRunArgs& A, const char* who) {
 void trace_class_dev(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, uint8_t* cls,
                      uint64_t* elem, uint64_t stream) {
   if (L <= 0) return;
-  if (((uintptr_t)text & 15) != 0) throw std::runtime_error("trace_class_dev: text must be 16-byte aligned");
-  if ((L + 255) / 256 > 0x7fffffffll) throw std::runtime_error("trace_class_dev: too many lines for one launch");
+  check_text_aligned(text, "trace_class_dev");
+  const unsigned blocks = launch_blocks(L, 256, "trace_class_dev", "lines");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_tr_class, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, text, tbytes, ls, ll, L, cls, elem);
-  LP_TRCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_tr_class, dim3(blocks), dim3(256), 0, st, text, tbytes, ls, ll, L, cls, elem);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void trace_class_host(const uint8_t* text, int64_t tbytes, const int64_t* ls, const int32_t* ll, int64_t L, uint8_t* cls,
@@ -213,11 +195,11 @@ void trace_runs_dev(const TraceRunArgs& A, void* tmp, uint64_t stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   TrAgg* tiles = reinterpret_cast<TrAgg*>(tmp);
   hipLaunchKernelGGL(k_tr_tiles, dim3((unsigned)nt), dim3(256), 0, st, A, tiles);
-  LP_TRCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_tr_prefix, dim3(1), dim3(256), 0, st, tiles, nt);
-  LP_TRCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_tr_emit, dim3((unsigned)nt), dim3(256), 0, st, A, (const TrAgg*)tiles);
-  LP_TRCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 // the same rows in line order, by the same combine one line at a time

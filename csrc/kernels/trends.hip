@@ -17,17 +17,12 @@
 #include "cell_table.h"
 #include "gaps_core.h"
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 #include "ts_core.h"
 
 namespace lp {
-
-#define LP_TRCHECK(x)                                                                                           \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
 
 namespace {
 using ull = unsigned long long;
@@ -35,8 +30,8 @@ using ull = unsigned long long;
 
 constexpr int LS_MAX_LINES = 2048;   // lines per block at most
 
-// A block owns `per_block` consecutive lines (k_lead_sig's structure), one lane per line and round;
-// nothing is compacted. The stamp comes first: its walk ends within the line's first 67 bytes, and
+// A block owns `per_block` consecutive lines (line_geom), one lane per line and round; nothing is
+// compacted. The stamp comes first: its walk ends within the line's first 67 bytes, and
 // the signature walk then finds the head of the line in cache.
 __global__ __launch_bounds__(256) void k_line_stamps(LineStampsArgs A, int per_block) {
   const int64_t base = (int64_t)blockIdx.x * per_block;
@@ -58,16 +53,11 @@ static void ls_check(const LineStampsArgs& A, const char* who) {
 void line_stamps_dev(const LineStampsArgs& A, uint64_t stream, int per_block) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   ls_check(A, "line_stamps_dev");
-  if (((uintptr_t)A.text & 15) != 0) throw std::runtime_error("line_stamps_dev: text must be 16-byte aligned");
+  check_text_aligned(A.text, "line_stamps_dev");
   if (A.nl <= 0) return;
-  // lines per block: enough blocks to spread a small document over the CUs, 2048 for big ones
-  int per = per_block;
-  if (per <= 0) per = (int)std::min<int64_t>(LS_MAX_LINES, std::max<int64_t>(256, A.nl / 2048));
-  per = (per + 255) / 256 * 256;
-  if (per > LS_MAX_LINES) throw std::runtime_error("line_stamps_dev: per_block must be at most 2048");
-  const int64_t blocks = (A.nl + per - 1) / per;
-  hipLaunchKernelGGL(k_line_stamps, dim3((unsigned)blocks), dim3(256), 0, st, A, per);
-  LP_TRCHECK(hipGetLastError());
+  const LineGeom g = line_geom(A.nl, per_block, LS_MAX_LINES, "line_stamps_dev");
+  hipLaunchKernelGGL(k_line_stamps, dim3(g.blocks), dim3(256), 0, st, A, g.per);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void line_stamps_host(const LineStampsArgs& A) {
@@ -85,36 +75,9 @@ void line_stamps_host(const LineStampsArgs& A) {
 
 namespace {
 
-// the slot of the cell with key `k`, claimed if the cell is new (gap_table.hip gt_claim on this
-// table's columns: 64-bit CAS on the key, linear probing, the side slot for the key that equals
-// the empty marker). -1 when every slot holds another key: counted in used[1]. A new slot is
-// counted in *fresh (the block's LDS counter, or null: the caller knows the count).
-__device__ __forceinline__ int64_t ct_claim(const CellTab& T, int64_t k, unsigned int* fresh) {
-  ull* key = reinterpret_cast<ull*>(T.key);
-  if (k == GT_EMPTY) {
-    if (atomicCAS(key + T.cap, 0ull, (ull)GT_EMPTY) == 0ull && fresh) atomicAdd(fresh, 1u);
-    return T.cap;
-  }
-  const int64_t mask = T.cap - 1;
-  int64_t s = (int64_t)(gt_hash(k) & (uint64_t)mask);
-  for (int64_t j = 0; j < T.cap; ++j) {
-    ull v = __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (v == (ull)GT_EMPTY) {
-      v = atomicCAS(key + s, (ull)GT_EMPTY, (ull)k);
-      if (v == (ull)GT_EMPTY) {
-        if (fresh) atomicAdd(fresh, 1u);
-        return s;
-      }
-    }
-    if (v == (ull)k) return s;
-    s = (s + 1) & mask;
-  }
-  atomicAdd(T.used + 1, 1ull);
-  return -1;
-}
-
-// `cnt` lines of the cell (sig, bucket), the smallest of them `line`, into slot s. Everyone who
-// flushes into a slot writes the same signature and bucket: plain stores.
+// `cnt` lines of the cell (sig, bucket), the smallest of them `line`, into slot s, the slot that
+// gt_claim (gap_table.h) gave for cell_key(sig, bucket). Everyone who flushes into a slot writes
+// the same signature and bucket: plain stores.
 __device__ __forceinline__ void ct_apply(const CellTab& T, int64_t s, int64_t sig, int64_t bucket, ull cnt,
                                          long long line) {
   T.sig[s] = sig;
@@ -175,7 +138,7 @@ __global__ __launch_bounds__(256) void k_cell_fold(CellTab T, const int64_t* __r
       }
     }
     if (!done) {
-      const int64_t t = ct_claim(T, k, &s_fresh);
+      const int64_t t = gt_claim(T, k, &s_fresh);
       if (t >= 0) ct_apply(T, t, s, b, 1ull, g);
     }
   }
@@ -183,7 +146,7 @@ __global__ __launch_bounds__(256) void k_cell_fold(CellTab T, const int64_t* __r
   for (int j = threadIdx.x; j < CT_LDS_SLOTS; j += (int)blockDim.x) {
     const ull k = lkey[j];
     if (k == (ull)GT_EMPTY) continue;
-    const int64_t t = ct_claim(T, (int64_t)k, &s_fresh);
+    const int64_t t = gt_claim(T, (int64_t)k, &s_fresh);
     if (t >= 0) ct_apply(T, t, lsig[j], lbkt[j], (ull)lcnt[j], lmin[j]);
   }
   __syncthreads();
@@ -200,7 +163,6 @@ constexpr int CR_SLOTS = 256 * CR_ROUNDS;
 __global__ __launch_bounds__(256) void k_cell_rows(CellTab T, CellRows R, int64_t out_cap, ull* cnt) {
   __shared__ int s_wave[4];
   __shared__ long long s_out;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t base = (int64_t)blockIdx.x * CR_SLOTS + (int)threadIdx.x;
   unsigned int occ = 0u;                      // bit r: slot base + 256 r is occupied
 #pragma unroll
@@ -208,26 +170,9 @@ __global__ __launch_bounds__(256) void k_cell_rows(CellTab T, CellRows R, int64_
     const int64_t s = base + 256 * r;
     if (s <= T.cap && ct_occupied(T, s)) occ |= 1u << r;
   }
-  // exclusive scan of the lanes' counts over the block (k_line_vals)
-  const int c = __popc(occ);
-  int incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int v = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += v;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int off = incl - c, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const int t = s_wave[w];
-    off += w < wave ? t : 0;
-    total += t;
-  }
-  if (threadIdx.x == 0) s_out = total ? (long long)atomicAdd(cnt, (ull)total) : 0;
-  __syncthreads();
-  int64_t o = s_out + off;
+  int total;
+  const int off = block_excl_count(__popc(occ), s_wave, total);
+  int64_t o = block_reserve(cnt, total, &s_out) + off;
 #pragma unroll
   for (int r = 0; r < CR_ROUNDS; ++r) {
     if (!(occ & (1u << r))) continue;
@@ -247,7 +192,7 @@ __global__ __launch_bounds__(256) void k_cell_rows(CellTab T, CellRows R, int64_
 __global__ __launch_bounds__(256) void k_cell_reinsert(CellTab T, CellRows R, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int64_t t = ct_claim(T, cell_key(R.sig[i], R.bucket[i]), nullptr);
+  const int64_t t = gt_claim(T, cell_key(R.sig[i], R.bucket[i]), nullptr);
   if (t < 0) return;
   T.sig[t] = R.sig[i];
   T.bucket[t] = R.bucket[i];
@@ -265,12 +210,6 @@ static void cr_check(const CellRows& R, const char* who) {
   if (!R.sig || !R.bucket || !R.count || !R.first) throw std::runtime_error(std::string(who) + ": missing row column");
 }
 
-static unsigned ct_blocks(int64_t n, int per, const char* who) {
-  const int64_t b = (n + per - 1) / per;
-  if (b > 0x7fffffffll) throw std::runtime_error(std::string(who) + ": too many items for one launch");
-  return (unsigned)b;
-}
-
 void cell_fold_dev(const CellTab& T, const int64_t* sig, const int64_t* eff, int64_t n, int64_t line_base, int64_t W,
                    uint64_t stream, int tile) {
   ct_check(T, "cell_fold_dev");
@@ -279,17 +218,17 @@ void cell_fold_dev(const CellTab& T, const int64_t* sig, const int64_t* eff, int
   if (tile <= 0) tile = (int)std::min<int64_t>(CT_TILE, std::max<int64_t>(256, (n / CT_BLOCKS + 255) / 256 * 256));
   if (tile < 256 || tile > CT_TILE || tile % 256) throw std::runtime_error("cell_fold_dev: tile must be 256..2048, a multiple of 256");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_cell_fold, dim3(ct_blocks(n, tile, "cell_fold_dev")), dim3(256), 0, st, T, sig, eff, n, line_base,
+  hipLaunchKernelGGL(k_cell_fold, dim3(launch_blocks(n, tile, "cell_fold_dev")), dim3(256), 0, st, T, sig, eff, n, line_base,
                      W, tile);
-  LP_TRCHECK(hipGetLastError());
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void cell_rows_dev(const CellTab& T, const CellRows& R, int64_t out_cap, unsigned long long* cnt, uint64_t stream) {
   ct_check(T, "cell_rows_dev");
   if (out_cap > 0) cr_check(R, "cell_rows_dev");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_cell_rows, dim3(ct_blocks(T.cap + 1, CR_SLOTS, "cell_rows_dev")), dim3(256), 0, st, T, R, out_cap, cnt);
-  LP_TRCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_cell_rows, dim3(launch_blocks(T.cap + 1, CR_SLOTS, "cell_rows_dev")), dim3(256), 0, st, T, R, out_cap, cnt);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void cell_reinsert_dev(const CellTab& T, const CellRows& R, int64_t n, uint64_t stream) {
@@ -297,8 +236,8 @@ void cell_reinsert_dev(const CellTab& T, const CellRows& R, int64_t n, uint64_t 
   if (n <= 0) return;
   cr_check(R, "cell_reinsert_dev");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_cell_reinsert, dim3(ct_blocks(n, 256, "cell_reinsert_dev")), dim3(256), 0, st, T, R, n);
-  LP_TRCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_cell_reinsert, dim3(launch_blocks(n, 256, "cell_reinsert_dev")), dim3(256), 0, st, T, R, n);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 // ---- host twins: the same table layout, one thread

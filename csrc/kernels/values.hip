@@ -1,8 +1,8 @@
 // Values report: which numbers do the line templates of a log carry, and where do they peak?
 // k_line_vals walks every line once (val_core.h line_vals_at: template signature and numeric
 // fields in one pass), writes the signature of every line and the values as compacted
-// (line, val_key(signature, field), value) triples -- 0..8 per line, in the structure of
-// k_line_keys (correlate.hip). The grouping of the triples is the table work of gap_table.hip.
+// (line, val_key(signature, field), value) triples -- 0..8 per line, on the block primitives of
+// lp_block.h. The grouping of the triples is the table work of gap_table.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,26 +11,21 @@
 #include <vector>
 
 #include "lp_api.h"
+#include "lp_block.h"
 #include "lp_core.h"
 #include "lp_host.h"
 #include "val_core.h"
 
 namespace lp {
 
-#define LP_VCHECK(x)                                                                                            \
-  do {                                                                                                          \
-    hipError_t e_ = (x);                                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-  } while (0)
-
 constexpr int VL_MAX_LINES = 2048;                  // lines per block at most
 constexpr int VL_ROUND = 256;                       // lines per round: one per lane
 constexpr int VL_STAGE = VL_ROUND * VAL_PER_LINE;   // triples of a round at most: 32 KiB of LDS
 
 // A block owns `per_block` consecutive lines, one lane per line and round. A round's lanes hold
-// 0..8 triples each: an exclusive scan of the counts (shuffles within the wave, the four wave
-// totals through LDS) gives every lane its place in the round's LDS stage, the block reserves the
-// round's output slots with ONE global atomic, and the stage is copied out coalesced.
+// 0..8 triples each: an exclusive scan of the counts (block_excl_count) gives every lane its place
+// in the round's LDS stage, the block reserves the round's output slots with ONE global atomic
+// (block_reserve), and the stage is copied out coalesced.
 __global__ __launch_bounds__(256) void k_line_vals(ValLinesArgs A, int per_block) {
   __shared__ int64_t l_key[VL_STAGE];
   __shared__ int32_t l_line[VL_STAGE];
@@ -38,7 +33,7 @@ __global__ __launch_bounds__(256) void k_line_vals(ValLinesArgs A, int per_block
   __shared__ int s_wave[4];
   __shared__ int s_hit;
   __shared__ long long s_out;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   if (threadIdx.x == 0) s_hit = 0;
   const int64_t base = (int64_t)blockIdx.x * per_block;
   int hit_w = 0;                              // this wave's lines with a value (every lane holds it)
@@ -53,22 +48,9 @@ __global__ __launch_bounds__(256) void k_line_vals(ValLinesArgs A, int per_block
     }
     const int c = __popc(V.mask);
     hit_w += __popcll(__ballot(c != 0));
-    // exclusive scan of c over the round
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();                          // (also: the previous round's copy-out has read the stage)
-    int off = incl - c, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int t = s_wave[w];
-      off += w < wave ? t : 0;
-      total += t;
-    }
+    // exclusive scan of c over the round (its barrier also: the previous round's copy-out has read the stage)
+    int total;
+    int off = block_excl_count(c, s_wave, total);
     // stage: off + c <= total <= VL_STAGE
 #pragma unroll
     for (int j = 0; j < VAL_PER_LINE; ++j) {
@@ -79,9 +61,7 @@ __global__ __launch_bounds__(256) void k_line_vals(ValLinesArgs A, int per_block
         ++off;
       }
     }
-    if (threadIdx.x == 0) s_out = total ? (long long)atomicAdd(A.cnt, (unsigned long long)total) : 0;
-    __syncthreads();
-    const int64_t o0 = s_out;
+    const int64_t o0 = block_reserve(A.cnt, total, &s_out);
     for (int j = threadIdx.x; j < total; j += VL_ROUND) {
       const int64_t o = o0 + j;
       if (o >= A.cap) break;                  // over capacity: counted above, the caller re-runs
@@ -89,8 +69,8 @@ __global__ __launch_bounds__(256) void k_line_vals(ValLinesArgs A, int per_block
       A.out_key[o] = l_key[j];
       A.out_val[o] = l_val[j];
     }
-    // (the next round's first barrier stands between this copy-out and its writes of the stage and
-    // of s_wave; s_out is written after that barrier)
+    // (the next round's scan barrier stands between this copy-out and its writes of the stage and
+    // of s_out; its write of s_wave comes after block_reserve's barrier of this round)
   }
   if (lane == 0 && hit_w) atomicAdd(&s_hit, hit_w);
   __syncthreads();
@@ -107,17 +87,11 @@ static void vl_check(const ValLinesArgs& A, const char* who) {
 void line_vals_dev(const ValLinesArgs& A, uint64_t stream, int per_block) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   vl_check(A, "line_vals_dev");
-  if (((uintptr_t)A.text & 15) != 0) throw std::runtime_error("line_vals_dev: text must be 16-byte aligned");
+  check_text_aligned(A.text, "line_vals_dev");
   if (A.nl <= 0) return;
-  // lines per block: enough blocks to spread a small document over the CUs, 2048 for big ones
-  int per = per_block;
-  if (per <= 0) per = (int)std::min<int64_t>(VL_MAX_LINES, std::max<int64_t>(256, A.nl / 2048));
-  per = (per + 255) / 256 * 256;
-  if (per > VL_MAX_LINES) throw std::runtime_error("line_vals_dev: per_block must be at most 2048");
-  const int64_t blocks = (A.nl + per - 1) / per;
-  if (blocks > 0x7fffffffll) throw std::runtime_error("line_vals_dev: too many lines for one launch");
-  hipLaunchKernelGGL(k_line_vals, dim3((unsigned)blocks), dim3(256), 0, st, A, per);
-  LP_VCHECK(hipGetLastError());
+  const LineGeom g = line_geom(A.nl, per_block, VL_MAX_LINES, "line_vals_dev");
+  hipLaunchKernelGGL(k_line_vals, dim3(g.blocks), dim3(256), 0, st, A, g.per);
+  LP_HIP_CHECK(hipGetLastError());
 }
 
 void line_vals_host(const ValLinesArgs& A) {
