@@ -99,7 +99,7 @@ def main() -> int:
 
     c_ms = _median_ms(report, 1, max(3, args.steps // 2), dev)
     rep = out["c"]
-    # the steps of ValueAccumulator._add_lines on the whole document's triples, each into a fresh table
+    # the steps of ValueAccumulator._add_piece on the whole document's triples, each into a fresh table
     g, v = line.long(), value.long()
     at = (g << 30) | v
     every = torch.arange(L, dtype=torch.int64, device=dev)

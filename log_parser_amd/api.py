@@ -215,9 +215,7 @@ class LogParser:
 
     def gaps_resident(self, resident, top: Optional[int] = 20, cover: str = "context") -> dict:
         """``gaps`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        acc = self.gap_accumulator(cover)
-        acc.add_resident(resident)
-        return acc.report(top)
+        return self.gaps_stream(resident, None, top, cover)       # (``_source`` passes a resident log through)
 
     def gaps_corpus(self, docs, top: Optional[int] = 20, cover: str = "context") -> dict:
         """Coverage-gap report of many documents (an iterable of str or bytes), each analysed on
@@ -266,9 +264,7 @@ class LogParser:
 
     def timeline_resident(self, resident, bucket_seconds: int = 60, max_buckets: int = 65536) -> dict:
         """``timeline`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        acc = self._timeline_accumulator(bucket_seconds, max_buckets)
-        acc.add_resident(resident)
-        return acc.report()
+        return self.timeline_stream(resident, None, bucket_seconds, max_buckets)
 
     # ---- novelty report -----------------------------------------------------------------------
     def baseline(self):
@@ -324,11 +320,7 @@ class LogParser:
     def novelty_resident(self, resident, baseline, top: Optional[int] = 20, order: str = "count",
                          errors_only: bool = False) -> dict:
         """``novelty`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        from .novelty import check_order
-        check_order(order)
-        acc = self._novelty_accumulator(baseline)
-        acc.add_resident(resident)
-        return acc.report(top, order, errors_only)
+        return self.novelty_stream(resident, baseline, None, top, order, errors_only)
 
     # ---- trace report -------------------------------------------------------------------------
     def traces(self, logs, top: Optional[int] = 20, order: str = "count", unexplained_only: bool = False) -> dict:
@@ -373,11 +365,7 @@ class LogParser:
     def traces_resident(self, resident, top: Optional[int] = 20, order: str = "count",
                         unexplained_only: bool = False) -> dict:
         """``traces`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        from .novelty import check_order
-        check_order(order)
-        acc = self._trace_accumulator()
-        acc.add_resident(resident)
-        return acc.report(top, order, unexplained_only)
+        return self.traces_stream(resident, None, top, order, unexplained_only)
 
     # ---- lead-up report -----------------------------------------------------------------------
     def leadup(self, logs, window: int = 50, top: Optional[int] = 20, order: str = "share", min_count: int = 2) -> dict:
@@ -429,11 +417,7 @@ class LogParser:
     def leadup_resident(self, resident, window: int = 50, top: Optional[int] = 20, order: str = "share",
                         min_count: int = 2) -> dict:
         """``leadup`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        from .leadup import check_args
-        check_args(window, order, min_count)
-        acc = self.leadup_accumulator(window)
-        acc.add_resident(resident)
-        return acc.report(top, order, min_count)
+        return self.leadup_stream(resident, None, window, top, order, min_count)
 
     # ---- values report -----------------------------------------------------------------------
     def values(self, logs, top: Optional[int] = 20, order: str = "peak", min_count: int = 5, min_fill: float = 0.9,
@@ -490,11 +474,7 @@ class LogParser:
     def values_resident(self, resident, top: Optional[int] = 20, order: str = "peak", min_count: int = 5,
                         min_fill: float = 0.9, varying: bool = True) -> dict:
         """``values`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        from .values import check_args
-        check_args(order, min_count, min_fill)
-        acc = self.value_accumulator()
-        acc.add_resident(resident)
-        return acc.report(top, order, min_count, min_fill, varying)
+        return self.values_stream(resident, None, top, order, min_count, min_fill, varying)
 
     # ---- trends report -----------------------------------------------------------------------
     def trends(self, logs, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
@@ -557,11 +537,7 @@ class LogParser:
                         kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,
                         max_buckets: int = 65536) -> dict:
         """``trends`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        from .trends import check_args, trends_stream
-        check_args(bucket_seconds, at, ratio, min_count, kind, order, max_buckets)
-        with self._engine_guard("trends"):
-            return trends_stream(self.engine, resident, None, bucket_seconds, at, ratio, min_count, kind, order, top,
-                                 max_buckets)
+        return self.trends_stream(resident, None, bucket_seconds, at, ratio, min_count, kind, order, top, max_buckets)
 
     # ---- pauses report -----------------------------------------------------------------------
     def pauses(self, logs, min_ms: int = 1000, by: str = "before", order: str = "total", min_count: int = 1,
@@ -622,11 +598,7 @@ class LogParser:
     def pauses_resident(self, resident, min_ms: int = 1000, by: str = "before", order: str = "total",
                         min_count: int = 1, top: Optional[int] = 20) -> dict:
         """``pauses`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
-        from .pauses import check_args, check_top
-        check_args(min_ms, by, order, min_count)
-        acc = self.pause_accumulator(min_ms, by, check_top(top))
-        acc.add_resident(resident)
-        return acc.report(order, min_count, top)
+        return self.pauses_stream(resident, None, min_ms, by, order, min_count, top)
 
     # ---- correlation report ------------------------------------------------------------------
     def correlate(self, logs, min_len: int = 8, top: Optional[int] = 20, order: str = "events", min_lines: int = 2,
@@ -676,10 +648,7 @@ class LogParser:
     def correlate_resident(self, resident, min_len: int = 8, top: Optional[int] = 20, order: str = "events",
                            min_lines: int = 2, max_share: float = 0.25) -> dict:
         """``correlate`` of a log held in HBM (``load_resident``), read in place twice."""
-        from .correlate import check_args, correlate_stream
-        check_args(min_len, order, min_lines, max_share)
-        with self._engine_guard("correlate"):
-            return correlate_stream(self.engine, resident, None, min_len, top, order, min_lines, max_share)
+        return self.correlate_stream(resident, None, min_len, top, order, min_lines, max_share)
 
     def validate(self, allow=("nfa",)) -> dict:
         """Compile report: library counts plus every regex that is invalid, routed to the host

@@ -26,37 +26,34 @@ one-document report at every chunk size. Nothing is scored and the frequency win
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 
+from .accumulator import U64, Examples
 from .engine import Engine
-from .gapreport import record_examples
 from .golden import correlate_check_args as check_args
 from .golden import correlate_row, line_key_tokens
 from .ops import kernels as K
-from .pieces import Piece, document_piece, gather_lines, stream_lines, stream_pieces
+from .pieces import Piece, document_piece, stream_lines, stream_pieces
 
-_U64 = (1 << 64) - 1
 _I64_MIN = -(1 << 63)
 
 
-def _lookup(key: torch.Tensor, table: K.GapTable, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+def _require(key: torch.Tensor, table: K.GapTable, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
     """(count, smallest ordinal) that ``table`` holds for every key of ``key``: all must be in it."""
-    t_key, t_count, t_first, _ = table.rows()
-    if t_key.numel() == 0:
+    count, first, found, groups = table.lookup(key)
+    if groups == 0:
         raise RuntimeError("correlate: the %s table is empty" % what)
-    t_key, o = torch.sort(t_key)
-    pos = torch.searchsorted(t_key, key).clamp(max=t_key.numel() - 1)
-    if not bool((t_key[pos] == key).all()):
+    if not bool(found.all()):
         raise RuntimeError("correlate: an event key is missing from the %s table (did the source change "
                            "between the passes?)" % what)
-    return t_count[o][pos], t_first[o][pos]
+    return count, first
 
 
 class _Correlation:
     """The tables of one report: ``add_events`` for every piece of pass 1, ``add_lines`` for every
-    run of lines of pass 2, then ``report``."""
+    piece of pass 2 (its events, if it has any, are not looked at), then ``report``."""
 
     def __init__(self, engine: Engine, min_len: int):
         self.engine, self.min_len = engine, int(min_len)
@@ -65,7 +62,7 @@ class _Correlation:
         self.last = K.GapTable(engine.device)           # (key, -line): minus the last of them
         self.lines = self.events = self.event_lines = 0
         self.walked = self.key_lines = 0
-        self._examples: Dict[int, Tuple[int, bytes]] = {}     # key -> (global line, raw line)
+        self._examples = Examples("correlate")          # key -> (global line, raw line)
 
     def add_events(self, piece: Piece) -> None:
         n, base = piece.ls.numel(), piece.line_base
@@ -79,20 +76,19 @@ class _Correlation:
         # (the signed 64-bit minimum of the table is the first event line)
         self.on_event.fold(key, line.long() + base, winners=False)
 
-    def add_lines(self, text, ls, ll, base: int, raw_lines: Callable[[torch.Tensor], List[bytes]]) -> None:
-        """``raw_lines(idx)``: the bytes of the lines ``idx`` of this run."""
-        self.walked += ls.numel()
-        if ls.numel() == 0:
+    def add_lines(self, piece: Piece) -> None:
+        self.walked += piece.ls.numel()
+        if piece.ls.numel() == 0:
             return
-        line, key, _, (m, held) = K.line_keys(text, ls, ll, table=self.on_event, min_len=self.min_len)
+        line, key, _, (m, held) = K.line_keys(piece.text, piece.ls, piece.ll, table=self.on_event, min_len=self.min_len)
         self.key_lines += held
         if m == 0:
             return
-        ordinal = line.long() + base
+        ordinal = line.long() + piece.line_base
         win = self.total.fold(key, ordinal)
         self.last.fold(key, -ordinal, winners=False)    # the table keeps a signed minimum: minus the last line
         if win.numel():
-            record_examples(self._examples, key, ordinal, win, raw_lines(line[win]))
+            self._examples.record(key, ordinal, win, piece.raw_lines(line[win]))
 
     def report(self, top: Optional[int], order: str, min_lines: int, max_share: float) -> dict:
         out = {"totalLines": self.lines, "events": self.events, "eventLines": self.event_lines,
@@ -103,8 +99,8 @@ class _Correlation:
             return out
         if self.walked != self.lines:
             raise RuntimeError("correlate: %d lines in the first pass, %d in the second" % (self.lines, self.walked))
-        n, first = _lookup(key, self.total, "line")
-        _, neg_last = _lookup(key, self.last, "last-line")
+        n, first = _require(key, self.total, "line")
+        _, neg_last = _require(key, self.last, "last-line")
         # (exact: line counts are far below 2^53, and Python compares the same way)
         keep = (n >= min_lines) & (n.double() <= max_share * self.lines)
         key, n_ev, first_ev, n, first, neg_last = (t[keep] for t in (key, n_ev, first_ev, n, first, neg_last))
@@ -121,15 +117,13 @@ class _Correlation:
             pick = pick[:max(0, int(top))]
         rows = torch.stack([key[pick], n_ev[pick], first_ev[pick], n[pick], first[pick], -neg_last[pick]]).cpu().tolist()
         for k, ne, fe, c, f, last in zip(*rows):
-            o, raw = self._examples[k]
-            if o != f:
-                raise RuntimeError("correlate: the example of %016x is not its first line" % (k & _U64))
+            raw = self._examples.take(k, f)
             if not (0 < ne <= c and f <= fe <= last):
                 raise RuntimeError("correlate: %016x has %d event lines of %d, lines %d / %d / %d"
-                                   % (k & _U64, ne, c, f, fe, last))
-            if (k & _U64) not in dict(line_key_tokens(raw, self.min_len)):
-                raise RuntimeError("correlate: line %d does not hold the key %016x" % (f + 1, k & _U64))
-            out["top"].append(correlate_row(k & _U64, ne, fe, c, f, last, raw, self.min_len))
+                                   % (k & U64, ne, c, f, fe, last))
+            if (k & U64) not in dict(line_key_tokens(raw, self.min_len)):
+                raise RuntimeError("correlate: line %d does not hold the key %016x" % (f + 1, k & U64))
+            out["top"].append(correlate_row(k & U64, ne, fe, c, f, last, raw, self.min_len))
         return out
 
 
@@ -142,7 +136,7 @@ def correlate_document(eng: Engine, text, n: int, data: bytes, min_len: int = 8,
     piece = document_piece(eng, text, n, data)
     acc.add_events(piece)
     if acc.on_event.used:
-        acc.add_lines(piece.text, piece.ls, piece.ll, 0, piece.raw_lines)
+        acc.add_lines(piece)
     return acc.report(top, order, min_lines, max_share)
 
 
@@ -159,8 +153,7 @@ def correlate_stream(eng: Engine, src, chunk_bytes: Optional[int] = None, min_le
         for piece in pieces:
             acc.add_events(piece)
     if acc.on_event.used:
-        with stream_lines(eng, src, chunk_bytes) as walk:
-            for text, ls, ll, base in walk:
-                acc.add_lines(text, ls, ll, base,
-                              lambda x, text=text, ls=ls, ll=ll: gather_lines(text, ls[x.long()], ll[x.long()]))
+        with stream_lines(eng, src, chunk_bytes) as pieces:
+            for piece in pieces:
+                acc.add_lines(piece)
     return acc.report(top, order, min_lines, max_share)

@@ -29,16 +29,16 @@ With ``cover="events"`` an event covers its own line only and both carries are e
 """
 from __future__ import annotations
 
-import contextlib
-from typing import Callable, Dict, Iterable, List, Optional, Tuple
+from typing import Callable, Iterable, List, Optional
 
 import numpy as np
 import torch
 
+from .accumulator import Accumulator, Examples
 from .engine import Engine
 from .golden import line_template
 from .ops import kernels as K
-from .pieces import Piece, document_piece, stream_pieces
+from .pieces import Piece, document_piece
 
 ORD_SHIFT = 40                      # ordinal = (document << ORD_SHIFT) | line
 ORD_LINE_MASK = (1 << ORD_SHIFT) - 1
@@ -72,19 +72,6 @@ def coverage(a: torch.Tensor, b: torch.Tensor, L: int) -> Optional[torch.Tensor]
     diff.scatter_add_(0, a, one)
     diff.scatter_add_(0, b, -one)
     return (diff[:L].cumsum(0) > 0).to(torch.uint8)
-
-
-def record_examples(examples: Dict[int, Tuple[int, bytes]], sig: torch.Tensor, ordinal: torch.Tensor,
-                    win: torch.Tensor, raws: List[bytes]) -> None:
-    """The examples of a fold's winners (``GapTable.fold``; novelty.py keeps its examples the same
-    way): ``examples[signature] = (ordinal, raw line)`` for every pair ``win[i]`` with the raw line
-    ``raws[i]``, unless the group already has an example with a smaller ordinal. One read of the
-    winners' signatures and ordinals; one winner per NEW template in steady state."""
-    sigs, ords = torch.stack([sig[win], ordinal[win]]).cpu().tolist()
-    for s, o, raw in zip(sigs, ords, raws):
-        cur = examples.get(s)
-        if cur is None or o < cur[0]:
-            examples[s] = (o, raw)
 
 
 def gaps_document(eng: Engine, text, n: int, data: bytes, top: Optional[int] = 20, cover: str = "context") -> dict:
@@ -124,7 +111,7 @@ def gaps_document(eng: Engine, text, n: int, data: bytes, top: Optional[int] = 2
     return out
 
 
-class GapAccumulator:
+class GapAccumulator(Accumulator):
     """Folds documents (``add_document``), streams (``add_stream``) and resident logs
     (``add_resident``) into one report; ``report`` renders it. An accumulator that has seen exactly
     one document reports what ``Engine.gaps_bytes`` reports for it; any other number of documents
@@ -135,12 +122,11 @@ class GapAccumulator:
         """``guard``: a context manager factory entered around every use of the engine (the
         parser's lock, ``LogParser.gap_accumulator``)."""
         check_cover(cover)
-        self.engine = engine
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
         self.cover = cover
         self.table = K.GapTable(engine.device)
         self.lines = self.events = self.error_lines = self.uncovered = self.documents = 0
-        self._examples: Dict[int, Tuple[int, bytes]] = {}     # signature -> (ordinal, raw line)
+        self._examples = Examples("GapAccumulator")     # signature -> (ordinal, raw line)
         before = engine.lib.ctx_before
         self._max_before = max(0, int(np.max(before))) if cover == "context" and len(before) else 0
 
@@ -164,16 +150,11 @@ class GapAccumulator:
             return
         mine = win[win < n]
         if mine.numel():
-            record_examples(self._examples, sig, ordinal, mine, fetch(mine))
+            self._examples.record(sig, ordinal, mine, fetch(mine))
         if held:
             for w in win[win >= n].tolist():
                 g, s, raw = held[w - n]
-                self._record(s, g + (doc << ORD_SHIFT), raw)
-
-    def _record(self, sig: int, ordinal: int, raw: bytes) -> None:
-        cur = self._examples.get(sig)
-        if cur is None or ordinal < cur[0]:
-            self._examples[sig] = (ordinal, raw)
+                self._examples.put(s, g + (doc << ORD_SHIFT), raw)
 
     def _new_document(self) -> int:
         doc = self.documents
@@ -182,23 +163,8 @@ class GapAccumulator:
         self.documents += 1
         return doc
 
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        """One document (str or bytes) in one piece."""
-        if isinstance(data, str):
-            data = data.encode("utf-8", errors="surrogateescape")
-        data = bytes(data)
-        with self._guard():
-            self._add_pieces([document_piece(self.engine, *self.engine.stage_text(data), data)])
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        """A bytes-like source (bytes, mmap, ``RepeatBuffer``) as ONE document, in chunks."""
-        with self._guard(), stream_pieces(self.engine, src, chunk_bytes) as pieces:
-            self._add_pieces(pieces)
-
-    def add_resident(self, res) -> None:
-        """A ``ResidentLog`` as ONE document, read in place chunk by chunk."""
-        self.add_stream(res)
+    def _line_base(self) -> int:
+        return 0                            # every source is a document of its own
 
     # ------------------------------------------------------------------ one document, piece by piece
     def _add_pieces(self, pieces: Iterable[Piece]) -> None:
@@ -208,9 +174,9 @@ class GapAccumulator:
         cov_until = 0                       # forward carry
         held: List[tuple] = []              # backward carry: (global line, signature, raw), ascending
         for piece in pieces:
-            cov_until, held = self._add_piece(doc, piece, cov_until, held)
+            cov_until, held = self._add_doc_piece(doc, piece, cov_until, held)
 
-    def _add_piece(self, doc: int, piece: Piece, cov_until: int, held: List[tuple]):
+    def _add_doc_piece(self, doc: int, piece: Piece, cov_until: int, held: List[tuple]):
         """Fold one piece of document ``doc``: takes and returns the two carries."""
         n, base, mb = piece.ls.numel(), piece.line_base, self._max_before
         if base + n > ORD_LINE_MASK:
@@ -269,9 +235,7 @@ class GapAccumulator:
             order = order[:max(0, int(top))]
         rows = torch.stack([count[order], first[order], sig[order], docs[order].long()]).cpu().tolist()
         for c, f, s, d in zip(*rows):
-            o, raw = self._examples[s]
-            if o != f:
-                raise RuntimeError("GapAccumulator: the example of %016x is not its first line" % (s & (2 ** 64 - 1)))
+            raw = self._examples.take(s, f)
             g = {"count": c, "firstLine": (f & ORD_LINE_MASK) + 1, "signature": "%016x" % (s & 0xFFFFFFFFFFFFFFFF),
                  "template": line_template(raw).decode("utf-8", errors="replace"),
                  "example": raw.decode("utf-8", errors="replace")}

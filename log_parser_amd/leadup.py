@@ -18,19 +18,15 @@ report for every chunk size. Nothing is scored and the frequency window is not t
 """
 from __future__ import annotations
 
-import contextlib
-from typing import Callable, Dict, Iterable, List, Optional, Tuple
+from typing import Callable, Iterable, List, Optional
 
 import torch
 
+from .accumulator import U64, Accumulator, Examples
 from .engine import Engine
-from .gapreport import record_examples
 from .golden import LEAD_MAX_WINDOW, line_template
-from .novelty import NoveltyAccumulator, _as_bytes
 from .ops import kernels as K
-from .pieces import Piece, document_piece, stream_pieces
-
-_U64 = (1 << 64) - 1
+from .pieces import Piece, document_piece
 
 
 def check_args(window: int, order: str = "share", min_count: int = 2) -> None:
@@ -42,7 +38,7 @@ def check_args(window: int, order: str = "share", min_count: int = 2) -> None:
         raise ValueError("min_count must be at least 1")
 
 
-class LeadupAccumulator:
+class LeadupAccumulator(Accumulator):
     """The lead-up report of ONE log: ``add_document``, ``add_stream`` (a bytes-like source in
     chunks) or ``add_resident`` (a ``ResidentLog``), then ``report``. Further sources continue the
     same log: the lines still pending at the end of one source can fall into the lead-up of an
@@ -55,29 +51,13 @@ class LeadupAccumulator:
         """``guard``: a context manager factory entered around every use of the engine (the
         parser's lock, ``LogParser.leadup_accumulator``)."""
         check_args(window)
-        self.engine, self.window = engine, int(window)
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
+        self.window = int(window)
         self.total = K.GapTable(engine.device)          # every line
         self.before = K.GapTable(engine.device)         # ... of the lead-up
         self.lines = self.events = self.event_lines = self.lead = 0
-        self._examples: Dict[int, Tuple[int, bytes]] = {}     # signature -> (global line, raw line)
+        self._examples = Examples("LeadupAccumulator")  # signature -> (global line, raw line)
         self._pending: List[tuple] = []                 # (global line, signature, raw), ascending
-
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        data = _as_bytes(data)
-        with self._guard():
-            # (a further source continues the log: one piece whose first line follows the lines so far)
-            piece = document_piece(self.engine, *self.engine.stage_text(data), data)
-            piece.line_base = self.lines
-            self._add_pieces([piece])
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard(), stream_pieces(self.engine, src, chunk_bytes, line_base=self.lines) as pieces:
-            self._add_pieces(pieces)
-
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
 
     def _add_pieces(self, pieces: Iterable[Piece], carry: bool = True) -> None:
         for piece in pieces:
@@ -115,12 +95,10 @@ class LeadupAccumulator:
             win = self.before.fold(pair_sig, ordinal)
             mine = win[win < n_lead]
             if mine.numel():
-                record_examples(self._examples, pair_sig, ordinal, mine, piece.raw_lines(line[mine]))
+                self._examples.record(pair_sig, ordinal, mine, piece.raw_lines(line[mine]))
             for w in (win[win >= n_lead].tolist() if came else ()):     # their carried bytes are the example
                 g, s, raw = came[w - n_lead]
-                cur = self._examples.get(s)
-                if cur is None or g < cur[0]:
-                    self._examples[s] = (g, raw)
+                self._examples.put(s, g, raw)
         if not carry:
             return
         # the tail that no event of this piece reaches: a later piece's event may
@@ -145,7 +123,7 @@ class LeadupAccumulator:
         out["templates"] = int(sig.numel())
         if sig.numel() == 0:
             return out
-        total, _ = NoveltyAccumulator._joined(sig, self.total)
+        total = self.total.lookup(sig)[0]
         keep = count >= min_count
         sig, count, first, total = sig[keep], count[keep], first[keep], total[keep]
         pick = torch.sort(first, stable=True)[1]                    # by first line (distinct per group)
@@ -158,13 +136,11 @@ class LeadupAccumulator:
             pick = pick[:max(0, int(top))]
         rows = torch.stack([count[pick], total[pick], first[pick], sig[pick]]).cpu().tolist()
         for c, t, f, s in zip(*rows):
-            o, raw = self._examples[s]
-            if o != f:
-                raise RuntimeError("LeadupAccumulator: the example of %016x is not its first line" % (s & _U64))
+            raw = self._examples.take(s, f)
             if not 0 < c <= t:
-                raise RuntimeError("LeadupAccumulator: %016x has %d lead-up lines of %d" % (s & _U64, c, t))
+                raise RuntimeError("LeadupAccumulator: %016x has %d lead-up lines of %d" % (s & U64, c, t))
             out["top"].append({"count": c, "total": t, "share": c / t, "lift": (c * self.lines) / (t * self.lead),
-                               "firstLine": f + 1, "signature": "%016x" % (s & _U64),
+                               "firstLine": f + 1, "signature": "%016x" % (s & U64),
                                "template": line_template(raw).decode("utf-8", errors="replace"),
                                "example": raw.decode("utf-8", errors="replace")})
         return out

@@ -19,21 +19,19 @@ Nothing is scored and the frequency window is not touched.
 from __future__ import annotations
 
 import contextlib
-from typing import Callable, Dict, Iterable, Optional, Tuple
+from typing import Callable, Optional
 
 import numpy as np
 import torch
 
+from .accumulator import U64, Accumulator, Examples
 from .engine import Engine
-from .gapreport import record_examples
 from .golden import line_template
 from .ops import kernels as K
-from .parallel.stream import document_chunks
-from .pieces import Piece, document_piece, stream_pieces
+from .pieces import Piece, as_bytes, document_piece, stream_lines
 
 FORMAT = 1                  # of a saved baseline
 FOLD_SLICE = 1 << 20        # pairs per fold of a baseline: its table follows the templates, not the lines
-_U64 = (1 << 64) - 1
 
 
 def check_order(order: str) -> None:
@@ -43,12 +41,6 @@ def check_order(order: str) -> None:
 
 def _same_device(a: torch.device, b: torch.device) -> bool:
     return a.type == b.type and (a.index or 0) == (b.index or 0)
-
-
-def _as_bytes(data) -> bytes:
-    if isinstance(data, str):
-        data = data.encode("utf-8", errors="surrogateescape")
-    return bytes(data)
 
 
 class Baseline:
@@ -93,7 +85,7 @@ class Baseline:
 
     def add_document(self, data) -> None:
         """One document (str or bytes), split by Java's rule (``K.split_lines``)."""
-        eng, data = self._engine(), _as_bytes(data)
+        eng, data = self._engine(), as_bytes(data)
         with self._guard():
             text, n = eng.stage_text(data)
             self._add_lines(text, *K.split_lines(text, n))
@@ -108,10 +100,9 @@ class Baseline:
         """A bytes-like source (bytes, mmap, ``RepeatBuffer``) or a ``ResidentLog`` as ONE document
         in chunks: only a chunk's own lines count, its halo lines belong to its neighbours."""
         eng = self._engine()
-        with self._guard(), contextlib.closing(document_chunks(eng, src, chunk_bytes)) as chunks:
-            for text, n, lh, rh, _, _ in chunks:
-                ls, ll = K.split_chunk_lines(text, n)
-                self._add_lines(text, ls[lh:ls.numel() - rh], ll[lh:ll.numel() - rh])
+        with self._guard(), stream_lines(eng, src, chunk_bytes) as pieces:
+            for piece in pieces:
+                self._add_lines(piece.text, piece.ls, piece.ll)
             self.documents += 1
 
     def add_resident(self, res) -> None:
@@ -123,7 +114,7 @@ class Baseline:
         int64 tensor of bit patterns, or Python ints (``golden.line_signature``'s unsigned values
         or their signed bit patterns)."""
         if not isinstance(signatures, torch.Tensor):
-            vals = [int(s) & _U64 for s in signatures]
+            vals = [int(s) & U64 for s in signatures]
             signatures = torch.tensor([v - (1 << 64) if v >> 63 else v for v in vals], dtype=torch.int64)
         with self._guard():
             return self.table.contains(signatures)
@@ -169,7 +160,7 @@ class Baseline:
         return b
 
 
-class NoveltyAccumulator:
+class NoveltyAccumulator(Accumulator):
     """The novelty report of ONE log against ``baseline``: ``add_document``, ``add_stream`` (a
     bytes-like source in chunks) or ``add_resident`` (a ``ResidentLog``), then ``report``. Further
     sources continue the same log.
@@ -185,33 +176,13 @@ class NoveltyAccumulator:
         parser's lock, ``LogParser.novelty_stream``)."""
         if not _same_device(baseline.device, engine.device):
             raise ValueError("novelty: the baseline lives on %s, the engine on %s" % (baseline.device, engine.device))
-        self.engine, self.baseline = engine, baseline
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
+        self.baseline = baseline
         self.table = K.GapTable(engine.device)          # every novel line
         self.err_table = K.GapTable(engine.device)      # ... that is a gap candidate
         self.ev_table = K.GapTable(engine.device)       # ... that an event lies on
         self.lines = self.events = self.error_lines = self.novel = self.novel_errors = 0
-        self._examples: Dict[int, Tuple[int, bytes]] = {}     # signature -> (global line, raw line)
-
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        data = _as_bytes(data)
-        with self._guard():
-            # (a further source continues the log: one piece whose first line follows the lines so far)
-            piece = document_piece(self.engine, *self.engine.stage_text(data), data)
-            piece.line_base = self.lines
-            self._add_pieces([piece])
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard(), stream_pieces(self.engine, src, chunk_bytes, line_base=self.lines) as pieces:
-            self._add_pieces(pieces)
-
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
-
-    def _add_pieces(self, pieces: Iterable[Piece]) -> None:
-        for piece in pieces:
-            self._add_piece(piece)
+        self._examples = Examples("NoveltyAccumulator")       # signature -> (global line, raw line)
 
     def _add_piece(self, piece: Piece) -> None:
         n, ne = piece.ls.numel(), piece.ev_line.numel()
@@ -233,7 +204,7 @@ class NoveltyAccumulator:
         ordinal = line.long() + piece.line_base
         win = self.table.fold(sig, ordinal)
         if win.numel():
-            record_examples(self._examples, sig, ordinal, win, piece.raw_lines(line[win]))
+            self._examples.record(sig, ordinal, win, piece.raw_lines(line[win]))
         if n_novel_cand:
             m = (flag & K.NV_CAND) != 0
             self.err_table.fold(sig[m], ordinal[m], winners=False)
@@ -248,16 +219,6 @@ class NoveltyAccumulator:
         with self._guard():
             return self._report(top, order, errors_only)
 
-    @staticmethod
-    def _joined(sig: torch.Tensor, table: K.GapTable) -> Tuple[torch.Tensor, int]:
-        """(the count ``table`` holds per signature of ``sig``, 0 where it holds none; its groups)."""
-        t_sig, t_count, _, _ = table.rows()
-        if t_sig.numel() == 0:
-            return torch.zeros_like(sig), 0
-        t_sig, o = torch.sort(t_sig)
-        pos = torch.searchsorted(t_sig, sig).clamp(max=t_sig.numel() - 1)
-        return torch.where(t_sig[pos] == sig, t_count[o][pos], 0), int(t_sig.numel())
-
     def _report(self, top: Optional[int], order: str, errors_only: bool) -> dict:
         b = self.baseline
         out = {"totalLines": self.lines, "events": self.events, "errorLines": self.error_lines,
@@ -267,8 +228,8 @@ class NoveltyAccumulator:
         out["templates"] = int(sig.numel())
         if sig.numel() == 0:
             return out
-        errs, out["errorTemplates"] = self._joined(sig, self.err_table)
-        evs, _ = self._joined(sig, self.ev_table)
+        errs, _, _, out["errorTemplates"] = self.err_table.lookup(sig)      # (no error line, no event: 0)
+        evs = self.ev_table.lookup(sig)[0]
         if errors_only:
             keep = errs > 0
             sig, count, first, errs, evs = sig[keep], count[keep], first[keep], errs[keep], evs[keep]
@@ -279,11 +240,9 @@ class NoveltyAccumulator:
             pick = pick[:max(0, int(top))]
         rows = torch.stack([count[pick], errs[pick], evs[pick], first[pick], sig[pick]]).cpu().tolist()
         for c, ce, cv, f, s in zip(*rows):
-            o, raw = self._examples[s]
-            if o != f:
-                raise RuntimeError("NoveltyAccumulator: the example of %016x is not its first line" % (s & _U64))
+            raw = self._examples.take(s, f)
             out["top"].append({"count": c, "errorLines": ce, "eventLines": cv, "firstLine": f + 1,
-                               "signature": "%016x" % (s & _U64),
+                               "signature": "%016x" % (s & U64),
                                "template": line_template(raw).decode("utf-8", errors="replace"),
                                "example": raw.decode("utf-8", errors="replace")})
         return out

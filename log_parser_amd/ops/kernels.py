@@ -906,49 +906,34 @@ def gap_lines(text, line_start, line_len, feat: torch.Tensor, cov: Optional[torc
 GT_EMPTY = -(1 << 63)       # empty marker of the key column (csrc/kernels/gap_table.h)
 GT_TILE = 2048              # pairs per block of k_gap_fold at most (small launches get smaller tiles)
 GT_LDS_SLOTS = 1024         # slots of its LDS table: more distinct signatures in a tile go to HBM directly
-_I64_MAX = (1 << 63) - 1
+I64_MAX = (1 << 63) - 1
 
 
-class GapTable:
-    """Device-resident groups of (signature, ordinal) pairs: per signature its count, its smallest
-    ordinal and the number of documents it occurs in, kept across ``fold`` calls (the chunks of a
-    stream, the documents of a corpus). GPU: k_gap_fold / k_gap_winners / k_gap_rows; CPU: their
-    host twins on the same layout.
+class _SlotTable:
+    """What the two device-resident hash tables share: the validation of ``cap`` / ``tile``, the
+    slot counter, the capacity rule with its growth, and the rows. A subclass has its columns
+    (``_alloc``, ``_tab``, ``_row_dtypes``), the names of its native calls and its ``fold``.
 
-    Capacity: before ``n`` pairs are folded, ``2 * (used + n) <= cap`` holds -- the table grows
+    Capacity: before ``n`` entries are folded, ``2 * (used + n) <= cap`` holds -- the table grows
     (rows of the old one re-inserted into one at least twice as large) when it does not. ``used``
-    is bounded on the host by the number of pairs folded so far; the device counter is read only
-    when that bound crosses the limit, so steady folding reads nothing but the winners' count."""
+    is bounded on the host by the number of entries folded so far; the device counter is read only
+    when that bound crosses the limit, so steady folding reads nothing of the table."""
+
+    _max_tile: int
+    _row_dtypes: tuple
+    _rows_op: str
+    _reinsert_op: str
 
     def __init__(self, device, cap: int = 1 << 12, tile: int = 0):
-        """``tile``: pairs per block of k_gap_fold (256..GT_TILE, a multiple of 256) instead of the
-        size the launch picks from its number of pairs (tests: the paths of a full-size tile
-        without millions of pairs)."""
-        cap = max(2, int(cap))
+        cap, name = max(2, int(cap)), type(self).__name__
         self.tile = int(tile)
-        if self.tile and (self.tile < 256 or self.tile > GT_TILE or self.tile % 256):
-            raise ValueError("GapTable: tile must be 256..%d, a multiple of 256" % GT_TILE)
+        if self.tile and (self.tile < 256 or self.tile > self._max_tile or self.tile % 256):
+            raise ValueError("%s: tile must be 256..%d, a multiple of 256" % (name, self._max_tile))
         if cap & (cap - 1):
-            raise ValueError("GapTable: cap must be a power of two")
+            raise ValueError("%s: cap must be a power of two" % name)
         self.device = torch.device(device)
         self._bound = 0             # host upper bound of the occupied slots
-        self._last_doc = -1
         self._alloc(cap)
-
-    def _alloc(self, cap: int) -> None:
-        dev = self.device
-        self.cap = cap
-        self._key = torch.full((cap + 1,), GT_EMPTY, dtype=torch.int64, device=dev)
-        self._key[cap] = 0          # the side slot of the signature that equals the marker: unclaimed
-        self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
-        self._first = torch.full((cap + 1,), _I64_MAX, dtype=torch.int64, device=dev)
-        self._docs = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
-        self._last = torch.full((cap + 1,), -1, dtype=torch.int32, device=dev)
-        self._used = torch.zeros(2, dtype=torch.int64, device=dev)
-
-    def _tab(self):
-        return (self._key.data_ptr(), self._count.data_ptr(), self._first.data_ptr(), self._docs.data_ptr(),
-                self._last.data_ptr(), self._used.data_ptr(), self.cap)
 
     @property
     def _cuda(self) -> bool:
@@ -959,32 +944,99 @@ class GapTable:
         """Occupied slots (a read of the device counter)."""
         used, lost = self._used.tolist()
         if lost:
-            raise RuntimeError("GapTable: %d pairs found no slot (capacity rule broken)" % lost)
+            raise RuntimeError("%s: %d entries found no slot (capacity rule broken)" % (type(self).__name__, lost))
         self._bound = used
         return used
 
     def _rows(self, n: int):
-        dev = self.device
-        cols = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
-                torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-                torch.empty(n, dtype=torch.int32, device=dev))
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-        N.gap_rows(self._tab(), tuple(c.data_ptr() for c in cols), n, cnt.data_ptr(), _s(self._key), self._cuda)
+        """Every column of the ``n`` occupied slots, in no particular order."""
+        cols = tuple(torch.empty(n, dtype=t, device=self.device) for t in self._row_dtypes)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        getattr(N, self._rows_op)(self._tab(), tuple(c.data_ptr() for c in cols), n, cnt.data_ptr(), _s(self._key),
+                                  self._cuda)
         if int(cnt.item()) != n:
-            raise RuntimeError("GapTable: %d occupied slots, the counter says %d" % (int(cnt.item()), n))
+            raise RuntimeError("%s: %d occupied slots, the counter says %d" % (type(self).__name__, int(cnt.item()), n))
         return cols
+
+    def _reinsert(self, rows, n: int) -> None:
+        """``n`` rows of distinct keys into the (empty) table."""
+        if n:
+            getattr(N, self._reinsert_op)(self._tab(), tuple(c.data_ptr() for c in rows), n, _s(self._key), self._cuda)
+            self._used[0] = n
+
+    @staticmethod
+    def _fit(cap: int, used: int, n: int) -> int:
+        while 2 * (used + n) > cap:
+            cap *= 2
+        return cap
+
+    def _reserve(self, n: int) -> None:
+        """The capacity rule, before ``n`` entries are folded."""
+        if 2 * (self._bound + n) > self.cap:
+            used = self.used                                    # the bound crossed the limit: the real count
+            cap = self._fit(self.cap, used, n)
+            if cap != self.cap:
+                rows = self._rows(used)
+                self._alloc(cap)
+                self._reinsert(rows, used)
+        self._bound += n
+
+
+class GapTable(_SlotTable):
+    """Device-resident groups of (signature, ordinal) pairs: per signature its count, its smallest
+    ordinal and the number of documents it occurs in, kept across ``fold`` calls (the chunks of a
+    stream, the documents of a corpus). GPU: k_gap_fold / k_gap_winners / k_gap_rows; CPU: their
+    host twins on the same layout. Capacity and growth: ``_SlotTable``; steady folding reads
+    nothing but the winners' count."""
+
+    _max_tile = GT_TILE
+    _row_dtypes = (torch.int64, torch.int64, torch.int64, torch.int32, torch.int32)
+    _rows_op, _reinsert_op = "gap_rows", "gap_reinsert"
+
+    def __init__(self, device, cap: int = 1 << 12, tile: int = 0):
+        """``tile``: pairs per block of k_gap_fold (256..GT_TILE, a multiple of 256) instead of the
+        size the launch picks from its number of pairs (tests: the paths of a full-size tile
+        without millions of pairs)."""
+        super().__init__(device, cap, tile)
+        self._last_doc = -1
+
+    def _alloc(self, cap: int) -> None:
+        dev = self.device
+        self.cap = cap
+        self._key = torch.full((cap + 1,), GT_EMPTY, dtype=torch.int64, device=dev)
+        self._key[cap] = 0          # the side slot of the signature that equals the marker: unclaimed
+        self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._first = torch.full((cap + 1,), I64_MAX, dtype=torch.int64, device=dev)
+        self._docs = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
+        self._last = torch.full((cap + 1,), -1, dtype=torch.int32, device=dev)
+        self._used = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def _tab(self):
+        return (self._key.data_ptr(), self._count.data_ptr(), self._first.data_ptr(), self._docs.data_ptr(),
+                self._last.data_ptr(), self._used.data_ptr(), self.cap)
 
     def rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(signature int64, count int64, smallest ordinal int64, documents int32) of every group,
         in no particular order."""
         return self._rows(self.used)[:4]
 
-    def _grow(self, used: int, cap: int) -> None:
-        rows = self._rows(used)
-        self._alloc(cap)
-        if used:
-            N.gap_reinsert(self._tab(), tuple(c.data_ptr() for c in rows), used, _s(self._key), self._cuda)
-            self._used[0] = used
+    def sorted_rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(signature, count, smallest ordinal) of every group, by signature (as a signed number)."""
+        key, count, first, _ = self.rows()
+        key, o = torch.sort(key)
+        return key, count[o], first[o]
+
+    def lookup(self, key: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+        """The join of ``key`` (int64[n], on the table's device) with the groups: (count, smallest
+        ordinal, found) per key -- 0, 0 and False for a key the table does not hold -- and the
+        number of groups of the table. One ``rows``; what a missing key means is the caller's."""
+        t_key, t_count, t_first = self.sorted_rows()
+        groups = t_key.numel()
+        if groups == 0:
+            return torch.zeros_like(key), torch.zeros_like(key), torch.zeros_like(key, dtype=torch.bool), 0
+        pos = torch.searchsorted(t_key, key).clamp(max=groups - 1)
+        found = t_key[pos] == key
+        return torch.where(found, t_count[pos], 0), torch.where(found, t_first[pos], 0), found, groups
 
     def fold(self, sig: torch.Tensor, ord: torch.Tensor, doc: int = 0, winners: bool = True) -> torch.Tensor:
         """Fold the pairs (sig[i], ord[i]) of document ``doc`` (one document per call, numbers never
@@ -1002,14 +1054,7 @@ class GapTable:
             return torch.empty(0, dtype=torch.int64, device=self.device)
         sig = sig.to(device=self.device, dtype=torch.int64).contiguous()
         ord = ord.to(device=self.device, dtype=torch.int64).contiguous()
-        if 2 * (self._bound + n) > self.cap:
-            used = self.used                                    # the bound crossed the limit: the real count
-            if 2 * (used + n) > self.cap:
-                cap = self.cap
-                while 2 * (used + n) > cap:
-                    cap *= 2
-                self._grow(used, cap)
-        self._bound += n
+        self._reserve(n)
         self._last_doc = doc
         tab, st = self._tab(), _s(self._key)
         N.gap_fold(tab, sig.data_ptr(), ord.data_ptr(), n, doc, st, self._cuda, self.tile)
@@ -1039,18 +1084,14 @@ class GapTable:
         if n and torch.unique(sig).numel() != n:
             raise ValueError("GapTable.from_signatures: duplicate signatures")
         if cap is None:
-            cap = 1 << 12
-            while 2 * n > cap:
-                cap *= 2
+            cap = cls._fit(1 << 12, 0, n)
         elif cap < n:
             raise ValueError("GapTable.from_signatures: cap below the number of signatures")
         tab = cls(device, cap=cap)
         if n:
             dev = tab.device
-            rows = (sig, torch.ones(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
-                    torch.ones(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
-            N.gap_reinsert(tab._tab(), tuple(c.data_ptr() for c in rows), n, _s(tab._key), tab._cuda)
-            tab._used[0] = n
+            tab._reinsert((sig, torch.ones(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                           torch.ones(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)), n)
             tab._bound = n
             tab._last_doc = 0
         return tab
@@ -1064,25 +1105,17 @@ CT_TILE = 2048              # lines per block of k_cell_fold at most
 CT_LDS_SLOTS = 1024         # slots of its LDS table: more distinct cells in a tile go to HBM directly
 
 
-class CellTable:
+class CellTable(_SlotTable):
     """Device-resident counts per cell (template signature, time bucket): per cell its lines and
     its smallest global line number, kept across ``fold`` calls (the chunks of a stream). The key
     column holds ``golden.trend_cell_key(sig, bucket)``. GPU: k_cell_fold / k_cell_rows /
-    k_cell_reinsert; CPU: their host twins on the same layout. Capacity rule, growth and the host
-    bound of ``used`` are ``GapTable``'s."""
+    k_cell_reinsert; CPU: their host twins on the same layout. Capacity and growth: ``_SlotTable``.
+    ``tile``: lines per block of k_cell_fold (256..CT_TILE, a multiple of 256) instead of the size
+    the launch picks from its number of lines (tests)."""
 
-    def __init__(self, device, cap: int = 1 << 12, tile: int = 0):
-        """``tile``: lines per block of k_cell_fold (256..CT_TILE, a multiple of 256) instead of
-        the size the launch picks from its number of lines (tests)."""
-        cap = max(2, int(cap))
-        self.tile = int(tile)
-        if self.tile and (self.tile < 256 or self.tile > CT_TILE or self.tile % 256):
-            raise ValueError("CellTable: tile must be 256..%d, a multiple of 256" % CT_TILE)
-        if cap & (cap - 1):
-            raise ValueError("CellTable: cap must be a power of two")
-        self.device = torch.device(device)
-        self._bound = 0             # host upper bound of the occupied slots
-        self._alloc(cap)
+    _max_tile = CT_TILE
+    _row_dtypes = (torch.int64,) * 4
+    _rows_op, _reinsert_op = "cell_rows", "cell_reinsert"
 
     def _alloc(self, cap: int) -> None:
         dev = self.device
@@ -1092,44 +1125,17 @@ class CellTable:
         self._sig = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
         self._bucket = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
         self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
-        self._first = torch.full((cap + 1,), _I64_MAX, dtype=torch.int64, device=dev)
+        self._first = torch.full((cap + 1,), I64_MAX, dtype=torch.int64, device=dev)
         self._used = torch.zeros(2, dtype=torch.int64, device=dev)
 
     def _tab(self):
         return (self._key.data_ptr(), self._sig.data_ptr(), self._bucket.data_ptr(), self._count.data_ptr(),
                 self._first.data_ptr(), self._used.data_ptr(), self.cap)
 
-    @property
-    def _cuda(self) -> bool:
-        return self.device.type == "cuda"
-
-    @property
-    def used(self) -> int:
-        """Occupied slots (a read of the device counter)."""
-        used, lost = self._used.tolist()
-        if lost:
-            raise RuntimeError("CellTable: %d lines found no slot (capacity rule broken)" % lost)
-        self._bound = used
-        return used
-
     def rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(signature, bucket, lines, smallest line) of every cell, int64 each, in no particular
         order; the bucket of a template's undated lines is ``CT_UNDATED``."""
-        n = self.used
-        cols = tuple(torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(4))
-        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
-        N.cell_rows(self._tab(), tuple(c.data_ptr() for c in cols), n, cnt.data_ptr(), _s(self._key), self._cuda)
-        if int(cnt.item()) != n:
-            raise RuntimeError("CellTable: %d occupied slots, the counter says %d" % (int(cnt.item()), n))
-        return cols
-
-    def _grow(self, cap: int) -> None:
-        rows = self.rows()
-        used = rows[0].numel()
-        self._alloc(cap)
-        if used:
-            N.cell_reinsert(self._tab(), tuple(c.data_ptr() for c in rows), used, _s(self._key), self._cuda)
-            self._used[0] = used
+        return self._rows(self.used)
 
     def fold(self, sig: torch.Tensor, eff: torch.Tensor, line_base: int, W: int) -> None:
         """Fold n consecutive lines into the table: line i has the signature ``sig[i]``, the
@@ -1140,20 +1146,13 @@ class CellTable:
             raise ValueError("CellTable.fold: sig and eff differ in length")
         if isinstance(W, bool) or int(W) < 1:
             raise ValueError("CellTable.fold: W must be >= 1")
-        if not 0 <= int(line_base) <= _I64_MAX - n:
+        if not 0 <= int(line_base) <= I64_MAX - n:
             raise ValueError("CellTable.fold: line_base out of range")
         if n == 0:
             return
         sig = sig.to(device=self.device, dtype=torch.int64).contiguous()
         eff = eff.to(device=self.device, dtype=torch.int64).contiguous()
-        if 2 * (self._bound + n) > self.cap:
-            used = self.used                                    # the bound crossed the limit: the real count
-            if 2 * (used + n) > self.cap:
-                cap = self.cap
-                while 2 * (used + n) > cap:
-                    cap *= 2
-                self._grow(cap)
-        self._bound += n
+        self._reserve(n)
         N.cell_fold(self._tab(), sig.data_ptr(), eff.data_ptr(), n, int(line_base), int(W), _s(self._key), self._cuda,
                     self.tile)
 
@@ -1419,7 +1418,7 @@ PS_MAX_ABS_TS = 1 << 61     # stamps lie within +-2^61, so that no step overflow
 
 def pause_stats(device) -> torch.Tensor:
     """Statistics of no line at all: what ``pause_scan`` adds a run to."""
-    return torch.tensor([0, 0, 0, _I64_MAX, -_I64_MAX - 1], dtype=torch.int64, device=device)
+    return torch.tensor([0, 0, 0, I64_MAX, -I64_MAX - 1], dtype=torch.int64, device=device)
 
 
 def pause_scan(ts: torch.Tensor, sig: torch.Tensor, min_ms: int, line_base: int = 0, carry=None,
@@ -1444,9 +1443,9 @@ def pause_scan(ts: torch.Tensor, sig: torch.Tensor, min_ms: int, line_base: int 
     L = ts.numel()
     if sig.dtype != torch.int64 or sig.numel() != L or not sig.is_contiguous() or sig.device != dev:
         raise ValueError("pause_scan: sig must be contiguous int64[L] on the device of ts")
-    if isinstance(min_ms, bool) or not isinstance(min_ms, int) or not 1 <= min_ms <= _I64_MAX:
+    if isinstance(min_ms, bool) or not isinstance(min_ms, int) or not 1 <= min_ms <= I64_MAX:
         raise ValueError("pause_scan: min_ms must be an integer >= 1")
-    if isinstance(line_base, bool) or not isinstance(line_base, int) or not 0 <= line_base <= _I64_MAX - L:
+    if isinstance(line_base, bool) or not isinstance(line_base, int) or not 0 <= line_base <= I64_MAX - L:
         raise ValueError("pause_scan: line_base out of range")
     if carry is not None:
         c_ts, c_line, c_sig = (int(x) for x in carry)

@@ -5,8 +5,8 @@ The stamped lines of a log in line order are ``i_0 < i_1 < ...``; the *step* k i
 ``i_k`` minus the stamp of ``i_{k-1}`` (its from-line and its to-line). A step below 0 runs
 backwards and is only counted, a step ``>= min_ms`` is a *pause*.
 
-:class:`PauseAccumulator` walks ONE log in runs of lines -- ``pieces.stream_lines``, for a staged
-document the line index alone; the matchers do not run. Per run:
+:class:`PauseAccumulator` walks ONE log in pieces without events (the walk without the matchers
+of ``accumulator.LineAccumulator``). Per run:
 
 * ``K.line_stamps``: signature and stamp of every line from one visit of the line;
 * ``K.pause_scan`` (k_ps_tiles / k_ps_prefix / k_ps_emit, csrc/kernels/pauses.hip): the pauses as
@@ -28,20 +28,17 @@ chunk size. Nothing is scored and the frequency window is not touched.
 """
 from __future__ import annotations
 
-import contextlib
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
+from .accumulator import U64, Examples, LineAccumulator
 from .engine import Engine
 from .golden import pauses_check_args as check_args
 from .golden import pauses_head, pauses_longest_row, pauses_order_key, pauses_template_row
-from .novelty import _as_bytes
 from .ops import kernels as K
-from .pieces import Piece, gather_lines, stream_lines
+from .pieces import Piece
 
-_U64 = (1 << 64) - 1
-_I64_MAX = (1 << 63) - 1
 
 
 def check_top(top, what: str = "top") -> Optional[int]:
@@ -60,14 +57,14 @@ def _group(key, count, total, peak, peak_line, first):
     n, dev = uk.numel(), key.device
     zeros = torch.zeros(n, dtype=torch.int64, device=dev)
     g_peak = zeros.clone().scatter_reduce_(0, inv, peak, "amax", include_self=False)
-    big = torch.full((n,), _I64_MAX, dtype=torch.int64, device=dev)
-    at_peak = torch.where(peak == g_peak[inv], peak_line, _I64_MAX)
+    big = torch.full((n,), K.I64_MAX, dtype=torch.int64, device=dev)
+    at_peak = torch.where(peak == g_peak[inv], peak_line, K.I64_MAX)
     return (uk, zeros.clone().index_add_(0, inv, count), zeros.clone().index_add_(0, inv, total), g_peak,
             big.clone().scatter_reduce_(0, inv, at_peak, "amin", include_self=True),
             big.clone().scatter_reduce_(0, inv, first, "amin", include_self=True))
 
 
-class PauseAccumulator:
+class PauseAccumulator(LineAccumulator):
     """The pauses report of ONE log: ``add_document``, ``add_stream`` (a bytes-like source in
     chunks) or ``add_resident`` (a ``ResidentLog``), then ``report``. Further sources continue the
     same log: their first line follows the lines so far. ``min_ms``, ``by`` and the length
@@ -80,8 +77,7 @@ class PauseAccumulator:
         parser's lock, ``LogParser.pause_accumulator``)."""
         check_args(min_ms, by)
         self.min_ms, self.by, self.longest = min_ms, by, check_top(longest, "longest")
-        self.engine = engine
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
         dev = engine.device
         self.by_template = K.GapTable(dev)      # (signature, g): lines per template
         self.stats = K.pause_stats(dev)
@@ -92,31 +88,10 @@ class PauseAccumulator:
         self.carry: Optional[Tuple[int, int, int]] = None      # (stamp, line, signature) of the last stamped line
         self._carry_raw = b""                                   # its bytes
         self._longest: List[tuple] = []     # (-ms, to-line, from-line, from-stamp, before, after), sorted
-        self._examples: Dict[int, Tuple[int, bytes]] = {}       # signature (signed) -> (first to-line, the key line)
+        self._examples = Examples("PauseAccumulator")           # signature (signed) -> (first to-line, the key line)
 
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        data = _as_bytes(data)
-        with self._guard():
-            text, n = self.engine.stage_text(data)
-            ls, ll = K.split_lines(text, n)
-            none = torch.empty(0, dtype=torch.int32, device=text.device)
-            # (a piece without events: for its raw_lines, which cuts the lines from the host copy)
-            self._add_lines(text, ls, ll, Piece(self.engine, text, ls, ll, none, none, 0, True, host=data).raw_lines)
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard(), stream_lines(self.engine, src, chunk_bytes, line_base=self.next_line) as walk:
-            for text, ls, ll, base in walk:
-                if base != self.next_line:
-                    raise RuntimeError("PauseAccumulator: a chunk starts at line %d, expected %d" % (base, self.next_line))
-                self._add_lines(text, ls, ll,
-                                lambda x, text=text, ls=ls, ll=ll: gather_lines(text, ls[x.long()], ll[x.long()]))
-
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
-
-    def _add_lines(self, text, ls, ll, raw_lines: Callable[[torch.Tensor], List[bytes]]) -> None:
-        """``raw_lines(idx)``: the bytes of the lines ``idx`` of this run."""
+    def _add_piece(self, piece: Piece) -> None:
+        text, ls, ll = piece.text, piece.ls, piece.ll
         n, base = ls.numel(), self.next_line
         if n == 0:
             return
@@ -165,7 +140,7 @@ class PauseAccumulator:
             fresh = list(zip(rest[:g], rest[g:2 * g], rest[2 * g:]))
             want += [x for _, _, x in fresh]
         here = sorted({x for x in want if x >= base})
-        raw = dict(zip(here, raw_lines(torch.tensor(here, dtype=torch.int64, device=dev) - base))) if here else {}
+        raw = dict(zip(here, piece.raw_lines(torch.tensor(here, dtype=torch.int64, device=dev) - base))) if here else {}
         if old is not None:
             raw[old[1]] = old_raw
         missing = [x for x in want if x not in raw]
@@ -174,7 +149,7 @@ class PauseAccumulator:
         if self.carry is not None and self.carry[1] >= base:
             self._carry_raw = raw[self.carry[1]]
         for s, first, x in fresh:
-            self._examples[s] = (first, raw[x])
+            self._examples.put(s, first, raw[x])      # (a new group: nothing is held for it yet)
         if cand:
             self._longest += [(-c_ms, c_to, c_from, from_ts, raw[c_from], raw[c_to]) for c_ms, c_to, c_from, from_ts in cand]
             self._longest.sort(key=lambda r: r[:2])
@@ -208,22 +183,17 @@ class PauseAccumulator:
         if int(count.sum()) != self.pauses:
             raise RuntimeError("PauseAccumulator: the groups hold %d pauses of %d" % (int(count.sum()), self.pauses))
         # the lines of the groups' templates, looked up on the device
-        t_sig, t_lines, _, _ = self.by_template.rows()
-        t_sig, o = torch.sort(t_sig)
-        at = torch.searchsorted(t_sig, key).clamp(max=t_sig.numel() - 1)
-        if not bool((t_sig[at] == key).all()):
+        t_lines, _, held, _ = self.by_template.lookup(key)
+        if not bool(held.all()):
             raise RuntimeError("PauseAccumulator: a group's template is not among the log's templates")
         keep = count >= min_count
-        cols = torch.stack([key, count, t_lines[o][at], total, peak, peak_line, first_line])[:, keep]
+        cols = torch.stack([key, count, t_lines, total, peak, peak_line, first_line])[:, keep]
         listed = [(pauses_order_key(order, c, lines, tot, mx, fl), (s, c, lines, tot, mx, ml, fl))
                   for s, c, lines, tot, mx, ml, fl in zip(*cols.cpu().tolist())]
         listed.sort(key=lambda kv: kv[0])
         for _, (s, c, lines, tot, mx, ml, fl) in cut(listed):
-            x, raw = self._examples[s]
-            if x != fl:
-                raise RuntimeError("PauseAccumulator: the example of %016x belongs to line %d, its first pause to %d"
-                                   % (s & _U64, x + 1, fl + 1))
-            out["templates"].append(pauses_template_row(s & _U64, c, lines, tot, mx, ml, fl, raw))
+            raw = self._examples.take(s, fl)
+            out["templates"].append(pauses_template_row(s & U64, c, lines, tot, mx, ml, fl, raw))
         return out
 
 

@@ -1,7 +1,9 @@
-"""The document walk of the reports that match a log without scoring it (gapreport.py, timeline.py).
+"""The source walk of the reports: every report that reads a log without scoring it loops over the
+pieces of this module (accumulator.py holds that loop).
 
-A *piece* is a run of consecutive lines of one document, with the events on them. A report is a
-loop over pieces; what differs between the two kinds of source stays in here:
+A *piece* is a run of consecutive lines of one document, with the events on them. What differs
+between the two kinds of source, and between a walk with the matchers and one without, stays in
+here:
 
 * :func:`document_piece`: a whole document is split by ``K.split_lines`` (Java's rule: no trailing
   empty lines), is one segment that owns every line, and hands ``prepare`` its host bytes;
@@ -9,8 +11,9 @@ loop over pieces; what differs between the two kinds of source stays in here:
   ``parallel.stream.document_chunks`` -- line-aligned, with ``lib.halo`` lines of the neighbours on
   either side, split by ``K.split_chunk_lines`` (nothing trimmed). ``prepare`` emits the events of
   a chunk's own lines only, and the piece is cut down to those lines; no halo leaves this module;
-* :func:`stream_lines`: the same chunks and the same lines without the matchers, for a report that
-  walks its source a second time (correlate.py).
+* :func:`document_lines` / :func:`stream_lines`: the same lines as pieces WITHOUT the matchers
+  (no events), for a report that needs none (values, trends, pauses, a baseline) or walks its
+  source a second time (correlate.py).
 
 An event of a neighbouring piece can still concern a line of this one: such carries belong to the
 report (``line_base`` and ``last`` are for them). Nothing is scored, no frequency window touched.
@@ -29,6 +32,13 @@ from .ops import kernels as K
 from .parallel.stream import document_chunks
 
 _N_OPEN = 1 << 62       # a stream's line count N is open while it is walked (as in ``StreamAnalyzer.run``)
+
+
+def as_bytes(data) -> bytes:
+    """A document given as str or bytes-like, as bytes."""
+    if isinstance(data, str):
+        data = data.encode("utf-8", errors="surrogateescape")
+    return bytes(data)
 
 
 def gather_lines(text: torch.Tensor, starts: torch.Tensor, lens: torch.Tensor) -> List[bytes]:
@@ -75,13 +85,22 @@ class Piece:
         return [self.host[s:s + k] for s, k in zip(a, m)]
 
 
+def _lines_piece(eng: Engine, text, ls, ll, line_base: int, last: bool, host: Optional[bytes] = None) -> Piece:
+    none = torch.empty(0, dtype=torch.int32, device=text.device)
+    return Piece(eng, text, ls, ll, none, none, line_base, last, host=host)
+
+
+def document_lines(eng: Engine, text: torch.Tensor, n: int, data: bytes) -> Piece:
+    """The one piece of a staged document WITHOUT the matchers: its lines and its host bytes."""
+    return _lines_piece(eng, text, *K.split_lines(text, n), 0, True, host=data)
+
+
 def document_piece(eng: Engine, text: torch.Tensor, n: int, data: bytes) -> Piece:
     """The one piece of a staged document (``text`` = ``stage_text(data)``'s buffer), matched as
     ``analyze_bytes`` matches it. Without lines: a piece without lines, and nothing is launched."""
     ls, ll = K.split_lines(text, n)
     if ls.numel() == 0:
-        none = torch.empty(0, dtype=torch.int32, device=text.device)
-        return Piece(eng, text, ls, ll, none, none, 0, True, host=data)
+        return _lines_piece(eng, text, ls, ll, 0, True, host=data)
     segs = Segments.single(ls.numel(), eng.device)
     prep = eng.prepare(text, n, ls, ll, segs, np.frombuffer(data, np.uint8) if n else None)
     return Piece(eng, text, ls, ll, prep.ev_line, prep.ev_pat, 0, True, host=data)
@@ -113,19 +132,17 @@ def _chunk_pieces(eng: Engine, chunks, line_base: int) -> Iterator[Piece]:
 
 
 @contextlib.contextmanager
-def stream_lines(eng: Engine, src, chunk_bytes: Optional[int] = None, line_base: int = 0):
-    """``with stream_lines(eng, src) as walk: for text, ls, ll, base in walk: ...`` -- the lines of
-    the source of ``stream_pieces`` WITHOUT the matchers: of every chunk its own lines (the halo
-    lines cut off) as their index in ``text`` and the document number ``base`` of the first. The
-    same chunks and the same lines as the pieces, for a report that walks its source a second
-    time and needs no events there (correlate.py)."""
+def stream_lines(eng: Engine, src, chunk_bytes: Optional[int] = None, line_base: int = 0) -> Iterator[Iterator[Piece]]:
+    """``with stream_lines(eng, src) as pieces: for piece in pieces: ...`` -- the pieces of
+    ``stream_pieces`` WITHOUT the matchers: the same chunks, of every chunk its own lines (the halo
+    lines cut off), the same ``line_base`` and ``last``, no events."""
     with contextlib.closing(document_chunks(eng, src, chunk_bytes)) as chunks:
-        yield _chunk_lines(chunks, line_base)
+        yield _chunk_lines(eng, chunks, line_base)
 
 
-def _chunk_lines(chunks, line_base: int):
-    for text, n, lh, rh, _host, _last in chunks:
+def _chunk_lines(eng: Engine, chunks, line_base: int) -> Iterator[Piece]:
+    for text, n, lh, rh, _host, last in chunks:
         ls, ll = K.split_chunk_lines(text, n)
         own_lo, own_hi = lh, ls.numel() - rh
-        yield text, ls[own_lo:own_hi], ll[own_lo:own_hi], line_base
+        yield _lines_piece(eng, text, ls[own_lo:own_hi], ll[own_lo:own_hi], line_base, last)
         line_base += own_hi - own_lo

@@ -17,18 +17,16 @@ frequency window is not touched.
 """
 from __future__ import annotations
 
-import contextlib
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
+from .accumulator import Accumulator
 from .engine import Engine
 from .golden import iso_ms, timeline_span_error
 from .ops import kernels as K
-from .pieces import Piece, document_piece, stream_pieces
-
-_I64_MAX = (1 << 63) - 1
+from .pieces import Piece, document_piece
 
 
 def check_bucket_args(bucket_seconds, max_buckets) -> Tuple[int, int]:
@@ -84,14 +82,14 @@ def timeline_piece(eng: Engine, st: TimelineState, piece: Piece) -> None:
     cand = ((feat & 9) != 0) & ((feat & 4) == 0) & dated            # golden.gap_candidate on a dated line
     first_cand = torch.where(cand, ar, n).min()
     nums = [stamped.sum(), dated.sum(), n_ooo[0],
-            torch.where(stamped, ts, _I64_MAX).min(), ts.max(), torch.where(dated, eff, _I64_MAX).min(), eff.max(),
+            torch.where(stamped, ts, K.I64_MAX).min(), ts.max(), torch.where(dated, eff, K.I64_MAX).min(), eff.max(),
             eff[-1], first_cand, eff[first_cand.clamp(max=n - 1)]]
     ev = ev_line.long()
     if ne:
         # event order is (line, pattern): the smallest and the largest key among the dated events
         key = ev * P + ev_pat.long()
         ev_dated = eff[ev] != NONE
-        k_lo, k_hi = torch.where(ev_dated, key, _I64_MAX).min(), torch.where(ev_dated, key, -1).max()
+        k_lo, k_hi = torch.where(ev_dated, key, K.I64_MAX).min(), torch.where(ev_dated, key, -1).max()
         nums += [ev_dated.sum(), k_lo, k_hi, eff[(k_lo // P).clamp(max=n - 1)], eff[(k_hi // P).clamp(min=0)]]
     nums = torch.stack(nums).tolist()
     n_stamped, n_dated, n_ooo, ts_lo, ts_hi, eff_lo, eff_hi, eff_last, c_first, c_time = nums[:10]
@@ -158,27 +156,23 @@ def timeline_document(eng: Engine, text, n: int, data: bytes, bucket_seconds: in
     return render(eng, st)
 
 
-class TimelineAccumulator:
-    """The timeline of ONE log fed in chunks: ``add_stream`` (a bytes-like source) or
+class TimelineAccumulator(Accumulator):
+    """The timeline of ONE log: ``add_document``, ``add_stream`` (a bytes-like source in chunks) or
     ``add_resident`` (a ``ResidentLog``), then ``report``. Further sources continue the same log."""
 
     def __init__(self, engine: Engine, bucket_seconds: int = 60, max_buckets: int = 65536,
                  guard: Optional[Callable] = None):
         """``guard``: a context manager factory entered around every use of the engine (the
         parser's lock, ``LogParser.timeline_stream``)."""
-        self.engine = engine
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
         self.state = TimelineState(*check_bucket_args(bucket_seconds, max_buckets))
 
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        eng, st = self.engine, self.state
-        # (a further source continues the log: its first line follows the lines so far)
-        with self._guard(), stream_pieces(eng, src, chunk_bytes, line_base=st.lines) as pieces:
-            for piece in pieces:            # (the span error leaves in the middle of the log)
-                timeline_piece(eng, st, piece)
+    @property
+    def lines(self) -> int:
+        return self.state.lines
 
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
+    def _add_piece(self, piece: Piece) -> None:
+        timeline_piece(self.engine, self.state, piece)      # (the span error leaves in the middle of the log)
 
     def report(self) -> dict:
         with self._guard():

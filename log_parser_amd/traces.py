@@ -20,19 +20,16 @@ next source continues the line numbers. Nothing is scored and the frequency wind
 """
 from __future__ import annotations
 
-import contextlib
-from typing import Callable, Dict, Iterable, List, Optional, Tuple
+from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from .accumulator import U64, Accumulator, Examples
 from .engine import Engine
-from .gapreport import record_examples
 from .golden import _TR_EXC
-from .novelty import NoveltyAccumulator, _as_bytes, check_order
+from .novelty import check_order
 from .ops import kernels as K
-from .pieces import Piece, document_piece, stream_pieces
-
-_U64 = (1 << 64) - 1
+from .pieces import Piece, document_piece
 
 
 def _text(raw: Optional[bytes], strip: bool = False) -> Optional[str]:
@@ -41,7 +38,7 @@ def _text(raw: Optional[bytes], strip: bool = False) -> Optional[str]:
     return (raw.strip(b" \t") if strip else raw).decode("utf-8", errors="replace")
 
 
-class TraceAccumulator:
+class TraceAccumulator(Accumulator):
     """The trace report of ONE log: ``add_document``, ``add_stream`` (a bytes-like source in
     chunks) or ``add_resident`` (a ``ResidentLog``), then ``report``. Further sources continue the
     same log's line numbers; a trace does not continue across sources."""
@@ -49,8 +46,7 @@ class TraceAccumulator:
     def __init__(self, engine: Engine, guard: Optional[Callable] = None):
         """``guard``: a context manager factory entered around every use of the engine (the
         parser's lock, ``LogParser.traces_stream``)."""
-        self.engine = engine
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
         self.table = K.GapTable(engine.device)          # every trace, by signature
         self.ev_table = K.GapTable(engine.device)       # ... that an event lies on
         self.lines = self.events = 0
@@ -60,22 +56,7 @@ class TraceAccumulator:
         # the lines of the open run read so far, and the last line of the previous piece (a head?)
         self._open: Dict[str, Optional[bytes]] = {"head": None, "top": None, "cause": None}
         self._prev_last: Optional[bytes] = None
-        self._examples: Dict[int, Tuple[int, tuple]] = {}      # signature -> (global start line, first trace)
-
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        data = _as_bytes(data)
-        with self._guard():
-            piece = document_piece(self.engine, *self.engine.stage_text(data), data)
-            piece.line_base = self.lines
-            self._add_pieces([piece])
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard(), stream_pieces(self.engine, src, chunk_bytes, line_base=self.lines) as pieces:
-            self._add_pieces(pieces)
-
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
+        self._examples = Examples("TraceAccumulator")          # signature -> (global start line, first trace)
 
     def _add_pieces(self, pieces: Iterable[Piece]) -> None:
         last = True
@@ -122,7 +103,7 @@ class TraceAccumulator:
         ordinal = start + line_base
         win = self.table.fold(sig.contiguous(), ordinal)
         if win.numel():
-            record_examples(self._examples, sig, ordinal, win, self._first_traces(cols[:, win], piece))
+            self._examples.record(sig, ordinal, win, self._first_traces(cols[:, win], piece))
         if self.events:
             self.ev_table.fold(sig[ev], ordinal[ev], winners=False)     # (no pair: nothing is launched)
 
@@ -199,7 +180,7 @@ class TraceAccumulator:
         out["groups"] = int(sig.numel())
         if sig.numel() == 0:
             return out
-        evs, ev_groups = NoveltyAccumulator._joined(sig, self.ev_table)
+        evs, _, _, ev_groups = self.ev_table.lookup(sig)
         out["unexplainedGroups"] = out["groups"] - ev_groups
         if unexplained_only:
             keep = evs == 0
@@ -211,12 +192,10 @@ class TraceAccumulator:
             pick = pick[:max(0, int(top))]
         rows = torch.stack([count[pick], evs[pick], first[pick], sig[pick]]).cpu().tolist()
         for c, cv, f, s in zip(*rows):
-            o, (n, frames, causes, headless, head, top_frame, cause) = self._examples[s]
-            if o != f:
-                raise RuntimeError("TraceAccumulator: the example of %016x is not its first trace" % (s & _U64))
+            n, frames, causes, headless, head, top_frame, cause = self._examples.take(s, f)
             exc = _TR_EXC.search(head) if head is not None else None
             out["top"].append({"count": c, "eventTraces": cv, "firstLine": f + 1 if headless else f,
-                               "signature": "%016x" % (s & _U64), "lines": n, "frames": frames, "causes": causes,
+                               "signature": "%016x" % (s & U64), "lines": n, "frames": frames, "causes": causes,
                                "head": _text(head), "exception": _text(exc.group()) if exc else None,
                                "topFrame": _text(top_frame, strip=True), "rootCause": _text(cause, strip=True)})
         return out

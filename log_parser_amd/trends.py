@@ -5,8 +5,8 @@ No baseline and no pattern: the log's own earlier part is the baseline. A *cell*
 signature, time bucket) with the number of lines in it; a pivot bucket splits the span of the log,
 and a template is judged by its dated lines before and from the pivot on.
 
-:class:`TrendAccumulator` walks ONE log in runs of lines -- ``pieces.stream_lines``, for a staged
-document the line index alone; the matchers do not run. Per run:
+:class:`TrendAccumulator` walks ONE log in pieces without events (the walk without the matchers
+of ``accumulator.LineAccumulator``). Per run:
 
 * ``K.line_stamps`` (k_line_stamps, csrc/kernels/trends.hip): signature and stamp of every line from
   one visit of the line;
@@ -25,22 +25,19 @@ the frequency window is not touched.
 """
 from __future__ import annotations
 
-import contextlib
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Optional
 
 import torch
 
+from .accumulator import U64, Examples, LineAccumulator
 from .engine import Engine
 from .golden import TREND_UNDATED, iso_ms, timeline_span_error
 from .golden import trends_check_args as check_args
 from .golden import (trends_head, trends_kind, trends_lift, trends_listed, trends_named_pivot, trends_order_key,
                      trends_pivot, trends_row)
-from .novelty import _as_bytes
 from .ops import kernels as K
-from .pieces import Piece, gather_lines, stream_lines
+from .pieces import Piece
 
-_U64 = (1 << 64) - 1
-_I64_MAX = (1 << 63) - 1
 NAMED_PIVOTS = ("first-event", "first-error")
 
 
@@ -50,7 +47,7 @@ def _segment_sum(x: torch.Tensor, start: torch.Tensor, end: torch.Tensor) -> tor
     return c[end] - c[start]
 
 
-class TrendAccumulator:
+class TrendAccumulator(LineAccumulator):
     """The trends report of ONE log: ``add_document``, ``add_stream`` (a bytes-like source in
     chunks) or ``add_resident`` (a ``ResidentLog``), then ``report``. Further sources continue the
     same log: their first line follows the lines so far. The bucket width is fixed when the
@@ -61,38 +58,16 @@ class TrendAccumulator:
         parser's lock, ``LogParser.trend_accumulator``)."""
         self.W = check_args(bucket_seconds)[0]
         self.bucket_seconds = int(bucket_seconds)
-        self.engine = engine
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
         dev = engine.device
         self.cells = K.CellTable(dev)
         self.by_template = K.GapTable(dev)      # (signature, g): lines per template, its first line
         self.next_line = 0
         self.carry_eff = K.TS_NONE              # effective time of the last line so far
-        self._examples: Dict[int, Tuple[int, bytes]] = {}     # signature (signed) -> (first line, its bytes)
+        self._examples = Examples("TrendAccumulator")         # signature (signed) -> (first line, its bytes)
 
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        data = _as_bytes(data)
-        with self._guard():
-            text, n = self.engine.stage_text(data)
-            ls, ll = K.split_lines(text, n)
-            none = torch.empty(0, dtype=torch.int32, device=text.device)
-            # (a piece without events: for its raw_lines, which cuts the examples from the host copy)
-            self._add_lines(text, ls, ll, Piece(self.engine, text, ls, ll, none, none, 0, True, host=data).raw_lines)
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard(), stream_lines(self.engine, src, chunk_bytes, line_base=self.next_line) as walk:
-            for text, ls, ll, base in walk:
-                if base != self.next_line:
-                    raise RuntimeError("TrendAccumulator: a chunk starts at line %d, expected %d" % (base, self.next_line))
-                self._add_lines(text, ls, ll,
-                                lambda x, text=text, ls=ls, ll=ll: gather_lines(text, ls[x.long()], ll[x.long()]))
-
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
-
-    def _add_lines(self, text, ls, ll, raw_lines: Callable[[torch.Tensor], List[bytes]]) -> None:
-        """``raw_lines(idx)``: the bytes of the lines ``idx`` of this run."""
+    def _add_piece(self, piece: Piece) -> None:
+        text, ls, ll = piece.text, piece.ls, piece.ll
         n, base = ls.numel(), self.next_line
         if n == 0:
             return
@@ -106,10 +81,7 @@ class TrendAccumulator:
         tail = torch.cat([eff[-1:], sig[win]]).cpu().tolist()
         self.carry_eff = tail[0]
         if win.numel():
-            for s, x, raw in zip(tail[1:], (win + base).cpu().tolist(), raw_lines(win)):
-                cur = self._examples.get(s)
-                if cur is None or x < cur[0]:
-                    self._examples[s] = (x, raw)
+            self._examples.put_all(tail[1:], (win + base).cpu().tolist(), piece.raw_lines(win))
 
     # ------------------------------------------------------------------ the report
     def report(self, at=None, ratio: int = 4, min_count: int = 5, kind: Optional[str] = None, order: str = "change",
@@ -141,8 +113,8 @@ class TrendAccumulator:
         sig, bucket, count, first = sig[o], bucket[o], count[o], first[o]
         dated = bucket != TREND_UNDATED
         dcount = torch.where(dated, count, 0)
-        n_dated, b0, b1 = torch.stack([dcount.sum(), torch.where(dated, bucket, _I64_MAX).min(),
-                                       torch.where(dated, bucket, -_I64_MAX).max()]).tolist()
+        n_dated, b0, b1 = torch.stack([dcount.sum(), torch.where(dated, bucket, K.I64_MAX).min(),
+                                       torch.where(dated, bucket, -K.I64_MAX).max()]).tolist()
         t_sig, t_len = torch.unique_consecutive(sig, return_counts=True)
         T = int(t_sig.numel())
         out = trends_head(total, n_dated, T, int(sig.numel()), self.bucket_seconds)
@@ -169,9 +141,9 @@ class TrendAccumulator:
         lead = start + (~dated[start]).long()                 # the template's first dated cell, if it has one
         peak = torch.zeros(T, dtype=torch.int64, device=sig.device).scatter_reduce_(0, seg, dcount, "amax", include_self=True)
         at_peak = dated & (dcount == peak[seg])
-        peak_bucket = torch.full((T,), _I64_MAX, dtype=torch.int64, device=sig.device).scatter_reduce_(
-            0, seg, torch.where(at_peak, bucket, _I64_MAX), "amin", include_self=True)
-        first_line = torch.full((T,), _I64_MAX, dtype=torch.int64, device=sig.device).scatter_reduce_(
+        peak_bucket = torch.full((T,), K.I64_MAX, dtype=torch.int64, device=sig.device).scatter_reduce_(
+            0, seg, torch.where(at_peak, bucket, K.I64_MAX), "amin", include_self=True)
+        first_line = torch.full((T,), K.I64_MAX, dtype=torch.int64, device=sig.device).scatter_reduce_(
             0, seg, first, "amin", include_self=True)
         cols = torch.stack([t_sig, lines, n, before, bucket[lead.clamp(max=sig.numel() - 1)], bucket[end - 1],
                             end - lead, peak_bucket, peak, first_line])
@@ -189,11 +161,8 @@ class TrendAccumulator:
         if top is not None:
             listed = listed[:max(0, int(top))]
         for _, (s, c_lines, c_n, c_before, c_after, fb, lb, active, pb, pc, fl, k, lift) in listed:
-            x, raw = self._examples[s]
-            if x != fl:
-                raise RuntimeError("TrendAccumulator: the example of %016x is line %d, its first line %d"
-                                   % (s & _U64, x + 1, fl + 1))
-            out["top"].append(trends_row(s & _U64, c_lines, c_n, c_before, c_after, fb, lb, active, pb, pc, fl, raw, W,
+            raw = self._examples.take(s, fl)
+            out["top"].append(trends_row(s & U64, c_lines, c_n, c_before, c_after, fb, lb, active, pb, pc, fl, raw, W,
                                          k, lift))
         return out
 

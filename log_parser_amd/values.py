@@ -7,8 +7,8 @@ stamp, and a *group* is (template signature, field number) under the 64-bit key 
 text kernel, k_line_vals (csrc/kernels/values.hip, the walk in val_core.h), signs every line and
 emits its values as (line, key, value) triples, 0..8 per line.
 
-:class:`ValueAccumulator` walks ONE log in runs of lines -- ``pieces.stream_lines``, for a staged
-document the line index alone; the matchers do not run -- and folds the triples of a run, with the
+:class:`ValueAccumulator` walks ONE log in pieces without events -- the walk without the
+matchers of ``accumulator.LineAccumulator`` -- and folds the triples of a run, with the
 global line ``g``, into five ``GapTable`` s (count and a signed 64-bit minimum per key):
 
 =============== ============================================ =====================================
@@ -28,32 +28,23 @@ scored and the frequency window is not touched.
 """
 from __future__ import annotations
 
-import contextlib
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Optional
 
 import torch
 
+from .accumulator import U64, Examples, LineAccumulator
 from .engine import Engine
 from .golden import VAL_MAX_LINES, VAL_PER_LINE, val_key
 from .golden import values_check_args as check_args
 from .golden import values_order_key, values_row
-from .novelty import _as_bytes
 from .ops import kernels as K
-from .pieces import Piece, gather_lines, stream_lines
+from .pieces import Piece
 
-_U64 = (1 << 64) - 1
 _LOW32 = 0xFFFFFFFF
 _LOW30 = (1 << 30) - 1
 
 
-def _sorted_rows(table: K.GapTable) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(key, count, smallest ordinal) of a table's groups, by key (as a signed number)."""
-    key, count, first, _ = table.rows()
-    key, o = torch.sort(key)
-    return key, count[o], first[o]
-
-
-class ValueAccumulator:
+class ValueAccumulator(LineAccumulator):
     """The values report of ONE log: ``add_document``, ``add_stream`` (a bytes-like source in
     chunks) or ``add_resident`` (a ``ResidentLog``), then ``report``. Further sources continue the
     same log: their first line follows the lines so far.
@@ -68,8 +59,7 @@ class ValueAccumulator:
         limit."""
         if isinstance(line_base, bool) or not isinstance(line_base, int) or not 0 <= line_base < VAL_MAX_LINES:
             raise ValueError("line_base must be an integer in [0, 2^32)")
-        self.engine = engine
-        self._guard = guard or contextlib.nullcontext
+        super().__init__(engine, guard)
         dev = engine.device
         self.by_template = K.GapTable(dev)      # (signature, g): lines per template
         self.lo = K.GapTable(dev)               # (key, value): count, min
@@ -80,31 +70,10 @@ class ValueAccumulator:
         self._sum = torch.empty(0, dtype=torch.int64, device=dev)
         self.line_base = self.next_line = int(line_base)
         self.values = self.value_lines = 0
-        self._examples: Dict[int, Tuple[int, int, bytes]] = {}    # key -> ((g << 30) | value, signature, raw line)
+        self._examples = Examples("ValueAccumulator")             # key -> ((g << 30) | value, (signature, raw line))
 
-    # ------------------------------------------------------------------ sources
-    def add_document(self, data) -> None:
-        data = _as_bytes(data)
-        with self._guard():
-            text, n = self.engine.stage_text(data)
-            ls, ll = K.split_lines(text, n)
-            none = torch.empty(0, dtype=torch.int32, device=text.device)
-            # (a piece without events: for its raw_lines, which cuts the examples from the host copy)
-            self._add_lines(text, ls, ll, Piece(self.engine, text, ls, ll, none, none, 0, True, host=data).raw_lines)
-
-    def add_stream(self, src, chunk_bytes: Optional[int] = None) -> None:
-        with self._guard(), stream_lines(self.engine, src, chunk_bytes, line_base=self.next_line) as walk:
-            for text, ls, ll, base in walk:
-                if base != self.next_line:
-                    raise RuntimeError("ValueAccumulator: a chunk starts at line %d, expected %d" % (base, self.next_line))
-                self._add_lines(text, ls, ll,
-                                lambda x, text=text, ls=ls, ll=ll: gather_lines(text, ls[x.long()], ll[x.long()]))
-
-    def add_resident(self, res) -> None:
-        self.add_stream(res)
-
-    def _add_lines(self, text, ls, ll, raw_lines: Callable[[torch.Tensor], List[bytes]]) -> None:
-        """``raw_lines(idx)``: the bytes of the lines ``idx`` of this run."""
+    def _add_piece(self, piece: Piece) -> None:
+        text, ls, ll = piece.text, piece.ls, piece.ll
         n, base = ls.numel(), self.next_line
         if base + n >= VAL_MAX_LINES:           # before anything is folded: the packed ordinals hold 32 bits of line
             raise ValueError("values: the log reaches line 2^32 (%d lines so far, %d more)" % (base, n))
@@ -128,10 +97,7 @@ class ValueAccumulator:
         if win.numel():
             # the lines that became their group's first: their bytes are its example, their signature its template
             rows = torch.stack([key[win], at[win], sig[line[win].long()]]).cpu().tolist()
-            for k, a, s, raw in zip(*rows, raw_lines(line[win])):
-                cur = self._examples.get(k)
-                if cur is None or a < cur[0]:
-                    self._examples[k] = (a, s, raw)
+            self._examples.put_all(rows[0], rows[1], zip(rows[2], piece.raw_lines(line[win])))
         # exact sums: this run's per key, merged into the running sorted pair
         uk, inv = torch.unique(key, return_inverse=True)
         part = torch.zeros(uk.numel(), dtype=torch.int64, device=dev).index_add_(0, inv, v)
@@ -157,10 +123,10 @@ class ValueAccumulator:
         out["templates"] = int(t_sig.numel())
         if self.values == 0:
             return out
-        key, count, vmin = _sorted_rows(self.lo)
+        key, count, vmin = self.lo.sorted_rows()
         cols = [key, count, vmin, self._sum]
         for table, what in ((self.hi, "max"), (self.first, "first-line"), (self.last, "last-line")):
-            k, c, o = _sorted_rows(table)
+            k, c, o = table.sorted_rows()
             if k.numel() != key.numel() or not bool((k == key).all()) or not bool((c == count).all()):
                 raise RuntimeError("ValueAccumulator: the %s table does not hold the groups of the count table" % what)
             cols.append(o)
@@ -169,23 +135,21 @@ class ValueAccumulator:
         out["fields"] = int(key.numel())
         per_sig = dict(zip(*torch.stack([t_sig, t_lines]).cpu().tolist()))
         groups = []
-        for k, c, lo, total, hi, first, last in zip(*torch.stack(cols).cpu().tolist()):
-            at, signed, raw = self._examples[k]
-            if at != first:
-                raise RuntimeError("ValueAccumulator: the example of %016x is not its first line" % (k & _U64))
+        rows = torch.stack(cols).cpu().tolist()
+        for k, c, lo, total, hi, first, last, (signed, raw) in zip(*rows, self._examples.take_all(rows[0], rows[5])):
             # the key says neither template nor field: the template is the one the kernel gave the example
             # line, the field the one whose key this is (values_row recomputes both from the line's bytes
             # for the rows that are listed)
-            sig = signed & _U64
-            j = next((j for j in range(VAL_PER_LINE) if val_key(sig, j) == k & _U64), None)
+            sig = signed & U64
+            j = next((j for j in range(VAL_PER_LINE) if val_key(sig, j) == k & U64), None)
             if j is None or signed not in per_sig:
                 raise RuntimeError("ValueAccumulator: line %d does not hold the field of the key %016x"
-                                   % ((first >> 30) + 1, k & _U64))
+                                   % ((first >> 30) + 1, k & U64))
             lines = per_sig[signed]
             vmax, max_line = (-hi) >> 32, _LOW32 - ((-hi) & _LOW32)
             if not (0 < c <= lines and lo <= vmax and lo * c <= total <= vmax * c):
                 raise RuntimeError("ValueAccumulator: %016x has %d values on %d lines, min %d, max %d, sum %d"
-                                   % (k & _U64, c, lines, lo, vmax, total))
+                                   % (k & U64, c, lines, lo, vmax, total))
             if c >= min_count and c >= min_fill * lines and (not varying or lo < vmax):
                 groups.append((values_order_key(order, sig, j, c, total, vmax, first >> 30),
                                (sig, j, c, total, lo, vmax, max_line, first >> 30, first & _LOW30,

@@ -273,7 +273,7 @@ def test_stream_and_resident_equal_document(case, tmp_path):
     want = _golden(lp, log, top=None)
     for chunk_bytes, pieces in ((1 << 20, 1), (len(data) // 3 + 200, 3), (len(data) // 40, None)):
         with stream_lines(lp.engine, data, chunk_bytes) as walk:
-            runs = [(ls.numel(), base) for _, ls, _, base in walk]
+            runs = [(p.ls.numel(), p.line_base) for p in walk]
         assert len(runs) == (pieces or len(runs)) and len(runs) >= (pieces or 40)
         assert sum(n for n, _ in runs) == 3000 and [b for _, b in runs] == [sum(n for n, _ in runs[:k]) for k in range(len(runs))]
         with stream_pieces(lp.engine, data, chunk_bytes) as ps:
@@ -281,7 +281,7 @@ def test_stream_and_resident_equal_document(case, tmp_path):
         assert lp.correlate_stream(data, chunk_bytes=chunk_bytes, top=None) == want, chunk_bytes
     head = "".join(log.splitlines(keepends=True)[:300])                            # one-line chunks
     with stream_lines(lp.engine, head.encode(), 64) as walk:
-        assert [ls.numel() for _, ls, _, _ in walk] == [1] * 300
+        assert [p.ls.numel() for p in walk] == [1] * 300
     assert lp.correlate_stream(head.encode(), chunk_bytes=64, top=None, min_lines=1) == _golden(lp, head, top=None, min_lines=1)
     for order in ("lines", "first"):
         assert lp.correlate_stream(data, chunk_bytes=5000, top=5, order=order, min_lines=4) == \
