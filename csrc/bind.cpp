@@ -1342,6 +1342,36 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("emit"), py::arg("ts"), py::arg("sig"), py::arg("L"), py::arg("line_base"), py::arg("min_ms"),
         py::arg("carry_ts"), py::arg("carry_line"), py::arg("carry_sig"), py::arg("tmp"), py::arg("head"),
         py::arg("rows"), py::arg("cap"), py::arg("stats"), py::arg("hist"), py::arg("stream"), py::arg("dev"));
+  // ---- cadence report (cadence.hip): beats per template; the tile rows, then their link
+  m.def("cadence_link_tmp_words", &cadence_link_tmp_words, py::arg("R"));
+  m.def("cadence_tile", [](uint64_t ts, uint64_t sig, int64_t L, int64_t line_base, uint64_t beat, uint64_t bkt,
+                           uint64_t rows, int64_t cap, uint64_t cnt, uint64_t s, bool dev) {
+    CadenceTileArgs A;
+    A.ts = P<const int64_t>(ts); A.sig = P<const int64_t>(sig); A.L = L; A.line_base = line_base;
+    A.beat = P<int64_t>(beat); A.bkt = P<int64_t>(bkt);
+    A.rows = P<int64_t>(rows); A.cap = cap; A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      cadence_tile_dev(A, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    cadence_tile_host(A); },
+        py::arg("ts"), py::arg("sig"), py::arg("L"), py::arg("line_base"), py::arg("beat"), py::arg("bkt"),
+        py::arg("rows"), py::arg("cap"), py::arg("cnt"), py::arg("stream"), py::arg("dev"));
+  m.def("cadence_link", [](uint64_t in, int64_t R, uint64_t out, int64_t cap, uint64_t head, uint64_t tmp,
+                           int64_t line_base, int64_t L, uint64_t beat, uint64_t bkt, uint64_t s, bool dev) {
+    CadenceLinkArgs A;
+    A.in = P<const int64_t>(in); A.R = R; A.out = P<int64_t>(out); A.cap = cap;
+    A.head = P<int64_t>(head); A.tmp = P<int64_t>(tmp);
+    A.line_base = line_base; A.L = L; A.beat = P<int64_t>(beat); A.bkt = P<int64_t>(bkt);
+    if (dev) {
+      cadence_link_dev(A, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    cadence_link_host(A); },
+        py::arg("in"), py::arg("R"), py::arg("out"), py::arg("cap"), py::arg("head"), py::arg("tmp"),
+        py::arg("line_base"), py::arg("L"), py::arg("beat"), py::arg("bkt"), py::arg("stream"), py::arg("dev"));
   // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
   m.def("ts_parse", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t L, uint64_t out, uint64_t s,
                        bool dev) {

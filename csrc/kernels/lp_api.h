@@ -627,6 +627,49 @@ void pause_count_host(const PauseArgs& A);
 void pause_emit_host(const PauseArgs& A);
 }  // namespace lp
 
+// ---- cadence report (cadence.hip): per stamped line the beat since the previous stamped line of its
+// template; one row per template, joined across tiles and runs
+namespace lp {
+// columns of a row: consecutive stamped occurrences of one signature. lines = beats + backward + 1;
+// sum / min / max speak of the forward beats (min INT64_MAX, max -1, max_from / max_to -1: none);
+// max_from / max_to: the lines of the first largest beat, max_to_ts the stamp of its to-line
+enum { CD_SIG = 0, CD_LINES = 1, CD_BEATS = 2, CD_BACKWARD = 3, CD_SUM = 4, CD_MIN = 5, CD_MAX = 6, CD_MAX_FROM = 7,
+       CD_MAX_TO = 8, CD_FIRST_LINE = 9, CD_LAST_LINE = 10, CD_LAST_TS = 11, CD_FIRST_TS = 12, CD_MAX_TO_TS = 13,
+       CD_COLS = 14 };
+struct CadenceTileArgs {
+  const int64_t* ts;         // [L] stamp of every line or TS_NONE, within +-2^61
+  const int64_t* sig;        // [L] template signature of every line
+  int64_t L;
+  int64_t line_base;         // global number of line 0
+  // beat[i]: the line's beat inside its tile of 2,048 lines, TS_NONE for an unstamped line and for
+  // the first stamped line of its signature in the tile; bkt[i]: bit length of a beat >= 0, else TS_NONE
+  int64_t* beat; int64_t* bkt;
+  // one row per (tile, signature), CD_COLS columns of `cap` entries each: the first `cap` of them;
+  // *cnt += all of them (above cap the caller reruns). GPU: in no particular order
+  int64_t* rows;
+  int64_t cap;
+  unsigned long long* cnt;
+};
+struct CadenceLinkArgs {
+  const int64_t* in;         // CD_COLS columns of R entries: rows sorted by (signature, first line)
+  int64_t R;
+  int64_t* out;              // CD_COLS columns of `cap` entries: one row per signature, sorted by signature
+  int64_t cap;
+  int64_t* head;             // [0] the output rows (all of them)
+  int64_t* tmp;              // device: cadence_link_tmp_words(R) words
+  // the run's lines: a row that follows one of its signature writes the beat of its first line
+  // when that line lies in [line_base, line_base + L)
+  int64_t line_base, L;
+  int64_t* beat; int64_t* bkt;
+};
+int64_t cadence_link_tmp_words(int64_t R);
+void cadence_tile_dev(const CadenceTileArgs& A, uint64_t stream);
+void cadence_link_dev(const CadenceLinkArgs& A, uint64_t stream);
+// rows per tile in the order of their first lines
+void cadence_tile_host(const CadenceTileArgs& A);
+void cadence_link_host(const CadenceLinkArgs& A);
+}  // namespace lp
+
 // ---- trace report (traces.hip): stack traces as runs of frame / cause lines, one row per trace
 #include "trace_core.h"
 namespace lp {

@@ -52,6 +52,12 @@
                                                where the log went silent: the steps between its
                                                stamped lines, the long ones with the lines around
                                                them and grouped by the template in front (JSON)
+  cadence   FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--min-ms N]
+            [--ratio R] [--min-count N] [--min-regularity F] [--kind missed|stopped|all]
+            [--order gap|overdue|count|first] [--top N]
+                                               the line templates that come at a steady beat: where
+                                               one missed beats while the log went on, and which
+                                               stopped before the log ended (JSON)
 
 Config keys use the reference names (``-Dpattern.directory=...``, env ``PATTERN_DIRECTORY``).
 """
@@ -261,6 +267,22 @@ def cmd_pauses(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_cadence(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    kw = {"min_ms": args.min_ms, "ratio": args.ratio, "min_count": args.min_count,
+          "min_regularity": args.min_regularity, "kind": args.kind, "order": args.order, "top": args.top}
+    try:
+        if args.stream:
+            rep = lp.cadence_stream(args.file, chunk_bytes=args.chunk_bytes, **kw)
+        else:
+            rep = lp.cadence_file(args.file, **kw)
+    except ValueError as e:                 # a threshold, a ratio or a share out of range
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     from .utils.launch import ensure_hw_queues
@@ -390,13 +412,33 @@ def main(argv: Optional[List[str]] = None) -> int:
     q.add_argument("--min-count", type=int, default=1, metavar="N",
                    help="list only the templates with at least N pauses (default 1)")
     q.add_argument("--top", type=int, default=20, help="pauses and templates reported (default 20)")
+    b = sub.add_parser("cadence", help="line templates of a log file that come at a steady beat, and the beats they missed")
+    b.add_argument("file")
+    _library_options(b)
+    b.add_argument("--stream", action="store_true", help="the file processed in chunks (same report)")
+    b.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    b.add_argument("--min-ms", type=int, default=1000, metavar="N",
+                   help="a hole is at least N milliseconds long, whatever the template's beat (default 1000)")
+    b.add_argument("--ratio", type=int, default=4, metavar="R",
+                   help="a hole is at least R times the template's typical beat (default 4)")
+    b.add_argument("--min-count", type=int, default=5, metavar="N",
+                   help="judge only the templates with at least N beats (default 5)")
+    b.add_argument("--min-regularity", type=float, default=0.8, metavar="F",
+                   help="a template is periodic when this share of its beats lies within a factor 4 (default 0.8)")
+    b.add_argument("--kind", choices=("missed", "stopped", "all"), default=None,
+                   help="list only the templates that missed beats, or that stopped, or every periodic one "
+                        "(default: missed or stopped)")
+    b.add_argument("--order", choices=("gap", "overdue", "count", "first"), default="gap",
+                   help="largest hole in beats of its template first (default), longest overdue first, most beats "
+                        "first, or in order of first appearance")
+    b.add_argument("--top", type=int, default=20, help="templates reported (default 20)")
     args = ap.parse_args(rest)
     logging.basicConfig(level=logging.WARNING, format="%(levelname)s [%(name)s] %(message)s")
     cfg = Config.load(overrides=overrides)
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
             "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values,
-            "trends": cmd_trends, "pauses": cmd_pauses}[args.cmd](args, cfg)
+            "trends": cmd_trends, "pauses": cmd_pauses, "cadence": cmd_cadence}[args.cmd](args, cfg)
 
 
 if __name__ == "__main__":

@@ -44,6 +44,7 @@ SOURCES = [
     ("kernels/timeline.hip", "hip"),
     ("kernels/trends.hip", "hip"),
     ("kernels/pauses.hip", "hip"),
+    ("kernels/cadence.hip", "hip"),
     ("kernels/traces.hip", "hip"),
     ("io/json_emit.cpp", "cpp"),
     ("io/docs.cpp", "cpp"),

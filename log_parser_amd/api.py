@@ -48,6 +48,10 @@ to embedders, with what an in-process user needs beyond one call at a time:
   long ones with the lines around them and grouped by the template in front of them --
   ``golden.pauses``; ``pauses_stream`` / ``pauses_resident`` for one log too large for one piece,
   ``pause_accumulator`` for a log that arrives over time;
+* ``cadence`` / ``cadence_file``: the line templates of a log that come at a steady beat, the
+  beats they missed and the ones that stopped before the log ended -- ``golden.cadence``;
+  ``cadence_stream`` / ``cadence_resident`` for one log too large for one piece,
+  ``cadence_accumulator`` for a log that arrives over time;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -599,6 +603,73 @@ class LogParser:
                         min_count: int = 1, top: Optional[int] = 20) -> dict:
         """``pauses`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
         return self.pauses_stream(resident, None, min_ms, by, order, min_count, top)
+
+    # ---- cadence report ----------------------------------------------------------------------
+    def cadence(self, logs, min_ms: int = 1000, ratio: int = 4, min_count: int = 5, min_regularity=0.8,
+                kind: Optional[str] = None, order: str = "gap", top: Optional[int] = 20) -> dict:
+        """Which line templates of one document (str or bytes) come at a steady beat -- a
+        heartbeat, a health check, a lease renewal -- and where did one go quiet while the rest of
+        the log went on? The *beat* of a stamped line is its stamp minus the stamp of the previous
+        stamped line of the same template; a beat below 0 is only counted (``backwardBeats``).
+        Per template: ``typicalMs``, the mean of its beats but the largest; ``regularity``, the
+        share of its beats within the best band a factor 4 wide (a periodic line scores about 1,
+        random arrivals below 0.5). A template is periodic with at least ``min_count`` beats,
+        ``typicalMs >= 1`` and ``regularity >= min_regularity``. It *missed* beats when its largest
+        beat ``maxMs`` (``fromLine`` / ``toLine`` / ``from`` / ``to``) is at least ``max(min_ms,
+        ratio * typicalMs)`` -- ``missedBeats`` says how many -- and it *stopped* when the time
+        from its last line to the log's last stamped line (``overdueMs``) is. ``kind``: None (the
+        templates that missed or stopped), ``"missed"``, ``"stopped"`` or ``"all"`` (the steady
+        ones too); ``order``: ``"gap"`` (the largest hole in beats of its template first),
+        ``"overdue"``, ``"count"`` or ``"first"``; ``top=None``: every one. The head counts the
+        lines, the templates and the periodic / missed / stopped ones. No pattern takes part.
+        ``Engine.cadence_bytes``; ``golden.cadence`` is the specification; the frequency window
+        is not touched."""
+        from .cadence import check_args, check_top
+        check_args(min_ms, ratio, min_count, min_regularity, kind, order)
+        check_top(top)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("pauses"):
+            return self.engine.cadence_bytes(logs, min_ms=min_ms, ratio=ratio, min_count=min_count,
+                                             min_regularity=min_regularity, kind=kind, order=order, top=top)
+
+    def cadence_file(self, path: str, min_ms: int = 1000, ratio: int = 4, min_count: int = 5, min_regularity=0.8,
+                     kind: Optional[str] = None, order: str = "gap", top: Optional[int] = 20) -> dict:
+        """``cadence`` of a log file, read as ONE document whatever its size."""
+        from .cadence import check_args, check_top
+        check_args(min_ms, ratio, min_count, min_regularity, kind, order)
+        check_top(top)
+        with open(path, "rb") as f:
+            return self.cadence(f.read(), min_ms, ratio, min_count, min_regularity, kind, order, top)
+
+    def cadence_accumulator(self):
+        """A ``cadence.CadenceAccumulator`` on this parser's engine for a log that arrives over
+        time (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then
+        ``report`` with the parameters of ``cadence``); each of its calls runs under the batcher
+        guard and the lock of ``pauses``."""
+        from .cadence import CadenceAccumulator
+        with self._engine_guard("pauses"):
+            return CadenceAccumulator(self.engine, guard=lambda: self._engine_guard("pauses"))
+
+    def cadence_stream(self, src_or_path, chunk_bytes: Optional[int] = None, min_ms: int = 1000, ratio: int = 4,
+                       min_count: int = 5, min_regularity=0.8, kind: Optional[str] = None, order: str = "gap",
+                       top: Optional[int] = 20) -> dict:
+        """``cadence`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). The templates' rows
+        stay on the device between the chunks; the report is exactly the one-document report,
+        whatever the chunk size."""
+        from .cadence import check_args, check_top
+        check_args(min_ms, ratio, min_count, min_regularity, kind, order)
+        check_top(top)
+        acc = self.cadence_accumulator()
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(min_ms, ratio, min_count, min_regularity, kind, order, top)
+
+    def cadence_resident(self, resident, min_ms: int = 1000, ratio: int = 4, min_count: int = 5, min_regularity=0.8,
+                         kind: Optional[str] = None, order: str = "gap", top: Optional[int] = 20) -> dict:
+        """``cadence`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        return self.cadence_stream(resident, None, min_ms, ratio, min_count, min_regularity, kind, order, top)
 
     # ---- correlation report ------------------------------------------------------------------
     def correlate(self, logs, min_len: int = 8, top: Optional[int] = 20, order: str = "events", min_lines: int = 2,

@@ -923,6 +923,15 @@ class Engine:
         from .pauses import pauses_document
         return pauses_document(self, bytes(data), min_ms, by, order, min_count, top)
 
+    # ------------------------------------------------------------------ cadence report
+    def cadence_bytes(self, data: bytes, min_ms: int = 1000, ratio: int = 4, min_count: int = 5, min_regularity=0.8,
+                      kind: Optional[str] = None, order: str = "gap", top: Optional[int] = 20) -> dict:
+        """Which line templates of one document come at a steady beat, where did one miss beats,
+        and which stopped before the end? (cadence.py; ``golden.cadence`` is the specification.)
+        The matchers do not run, nothing is scored and the frequency window is not touched."""
+        from .cadence import cadence_document
+        return cadence_document(self, bytes(data), min_ms, ratio, min_count, min_regularity, kind, order, top)
+
     # ------------------------------------------------------------------ trace report
     def traces_bytes(self, data: bytes, top: Optional[int] = 20, order: str = "count",
                      unexplained_only: bool = False) -> dict:

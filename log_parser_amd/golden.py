@@ -1278,6 +1278,180 @@ def pauses(logs, min_ms: int = 1000, by: str = "before", order: str = "total", m
 
 
 # ---------------------------------------------------------------------------------------------
+# Cadence report (an extra, as the gap report): which line templates come at a steady beat -- a
+# heartbeat, a health check, a lease renewal, a poller -- where did one of them miss beats while the
+# rest of the log went on, and which never came back before the log ended? ``pauses`` sees only the
+# steps of the whole log, ``trends`` only one pivot; here every template has a clock of its own.
+# These functions are the specification of ``log_parser_amd/cadence.py`` and of the beat scan
+# (csrc/kernels/cadence.hip).
+#
+# Known limits: only the stamps of ``line_timestamp`` count; stamps lie within +-2^61 ms, so no beat
+# overflows 64 bits; a template is the first ``SIG_MAX_BYTES`` bytes of a line; a line that comes in
+# bursts of a steady size looks periodic to ``regularity``, which sees a histogram and no order.
+
+CADENCE_ORDERS = ("gap", "overdue", "count", "first")
+CADENCE_KINDS = ("missed", "stopped")
+
+
+def cadence_check_args(min_ms=1000, ratio=4, min_count=5, min_regularity=0.8, kind: Optional[str] = None,
+                       order: str = "gap") -> Fraction:
+    """``min_regularity`` as an exact fraction, or ValueError."""
+    if isinstance(min_ms, bool) or not isinstance(min_ms, int) or min_ms < 1:
+        raise ValueError("cadence: min_ms must be an integer >= 1")
+    if isinstance(ratio, bool) or not isinstance(ratio, int) or ratio < 1:
+        raise ValueError("cadence: ratio must be an integer >= 1")
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+        raise ValueError("cadence: min_count must be an integer >= 1")
+    if isinstance(min_regularity, bool) or not isinstance(min_regularity, (int, float, Fraction)) \
+            or min_regularity != min_regularity or not 0 <= min_regularity <= 1:
+        raise ValueError("cadence: min_regularity must be a number in [0, 1]")
+    if kind is not None and kind != "all" and kind not in CADENCE_KINDS:
+        raise ValueError("cadence: kind must be None, 'all', 'missed' or 'stopped'")
+    if order not in CADENCE_ORDERS:
+        raise ValueError("cadence: order must be 'gap', 'overdue', 'count' or 'first'")
+    return Fraction(min_regularity)
+
+
+def cadence_regularity(hist: Sequence[int], beats: int) -> Fraction:
+    """The share of the forward beats in the best pair of adjacent buckets of ``hist`` (64 counts
+    by ``pause_bucket``): a band a factor 4 wide."""
+    h = list(hist) + [0]
+    return Fraction(max(h[b] + h[b + 1] for b in range(len(h) - 1)), beats)
+
+
+def cadence_judge(beats: int, sum_ms: int, max_ms: int, last_ts: int, end: int, hist: Sequence[int], min_ms: int,
+                  ratio: int, min_count: int, min_regularity: Fraction) -> Optional[dict]:
+    """What the numbers of one template say, or None when it is not periodic: ``typicalMs`` (the
+    mean of the beats but the largest), ``regularity``, ``overdueMs``, ``missed`` / ``missedBeats``
+    and ``stopped``. Exact arithmetic."""
+    if beats < min_count or beats < 2:
+        return None
+    typical = (sum_ms - max_ms) // (beats - 1)
+    if typical < 1:
+        return None
+    reg = cadence_regularity(hist, beats)
+    if reg < min_regularity:
+        return None
+    overdue = max(0, end - last_ts)
+    threshold = max(min_ms, ratio * typical)
+    missed = max_ms >= threshold
+    return {"typicalMs": typical, "regularity": reg, "overdueMs": overdue, "missed": missed,
+            "missedBeats": max_ms // typical - 1 if missed else 0, "stopped": overdue >= threshold}
+
+
+def cadence_listed(kind: Optional[str], missed: bool, stopped: bool) -> bool:
+    """A periodic template is listed under the filter ``kind`` (None: it missed beats or stopped)."""
+    if kind == "all":
+        return True
+    if kind is None:
+        return missed or stopped
+    return missed if kind == "missed" else stopped
+
+
+def cadence_order_key(order: str, typical: int, max_ms: int, overdue: int, beats: int, first_line: int):
+    """The sort key of a template: exact arithmetic (ints and ``Fraction``); ties by ``firstLine``."""
+    if order == "gap":
+        return (-Fraction(max(max_ms, overdue), typical), first_line)
+    if order == "overdue":
+        return (-overdue, first_line)
+    if order == "count":
+        return (-beats, first_line)
+    return (first_line,)
+
+
+def cadence_head(total: int, stamped: int, templates: int, first: Optional[int], last: Optional[int]) -> dict:
+    """The head of the report (``first`` / ``last``: the stamps of the first and the last stamped
+    line in line order, None without one); nothing judged or listed yet."""
+    return {"totalLines": total, "stampedLines": stamped, "templates": templates, "periodic": 0, "missed": 0,
+            "stopped": 0, "firstTimestamp": None if first is None else iso_ms(first),
+            "lastTimestamp": None if last is None else iso_ms(last), "top": []}
+
+
+def cadence_row(sig: int, lines: int, beats: int, backward: int, sum_ms: int, min_ms: int, max_ms: int, from_line: int,
+                to_line: int, to_ts: int, first_line: int, last_line: int, last_ts: int, hist: Sequence[int],
+                judged: dict, raw: bytes) -> dict:
+    """One row of the report from its numbers (lines 0-based), what ``cadence_judge`` said of them
+    and the template's first stamped line: ValueError unless that line has the template ``sig``."""
+    if line_signature(raw) != sig:
+        raise ValueError("cadence: line %d does not have the template %016x" % (first_line + 1, sig))
+    return {"signature": "%016x" % sig, "missed": judged["missed"], "stopped": judged["stopped"], "lines": lines,
+            "beats": beats, "backwardBeats": backward, "typicalMs": judged["typicalMs"],
+            "regularity": float(judged["regularity"]), "sumMs": sum_ms, "minMs": min_ms, "maxMs": max_ms,
+            "fromLine": from_line + 1, "toLine": to_line + 1, "from": iso_ms(to_ts - max_ms), "to": iso_ms(to_ts),
+            "missedBeats": judged["missedBeats"], "overdueMs": judged["overdueMs"], "firstLine": first_line + 1,
+            "lastLine": last_line + 1, "lastTimestamp": iso_ms(last_ts),
+            "intervals": [{"fromMs": (1 << b) >> 1, "toMs": 1 << b, "count": c} for b, c in enumerate(hist) if c],
+            "template": line_template(raw).decode("utf-8", errors="replace"),
+            "example": raw.decode("utf-8", errors="replace")}
+
+
+def cadence(logs, min_ms: int = 1000, ratio: int = 4, min_count: int = 5, min_regularity=0.8,
+            kind: Optional[str] = None, order: str = "gap", top: Optional[int] = 20) -> dict:
+    """The cadence report of ``logs`` (str or bytes). The stamped lines of ONE template signature
+    in line order are ``j_0 < j_1 < ...``; the beat k is ``own[j_k] - own[j_{k-1}]`` with the
+    from-line ``j_{k-1}`` and the to-line ``j_k``. A beat below 0 is a backward beat: counted,
+    nothing else. Per template: ``lines`` (stamped), ``beats`` (forward), ``backwardBeats``,
+    ``sumMs``, ``minMs``, ``maxMs`` with its lines and their stamps (the smallest to-line on a
+    tie), ``firstLine`` / ``lastLine`` / ``lastTimestamp`` and ``intervals``, the forward beats by
+    ``pause_bucket``. ``cadence_judge`` derives ``typicalMs``, ``regularity`` and ``overdueMs``
+    (against the stamp of the log's last stamped line) and says whether the template is periodic,
+    missed beats (``maxMs >= max(min_ms, ratio * typicalMs)``) or stopped (``overdueMs`` at least
+    that). Listed are the periodic templates of the kind ``kind`` (``cadence_listed``) in
+    ``order`` (``cadence_order_key``), ``top`` of them, each with its first stamped line as the
+    example. The head counts the periodic templates and those that missed / stopped, listed or not."""
+    min_reg = cadence_check_args(min_ms, ratio, min_count, min_regularity, kind, order)
+    raws = [line.encode("utf-8", errors="surrogateescape") for line in split_lines(_as_text(logs))]
+    per: Dict[int, dict] = {}
+    seen = set()
+    first_ts = end = None
+    stamped = 0
+    for i, raw in enumerate(raws):
+        sig = line_signature(raw)
+        seen.add(sig)
+        t = line_timestamp(raw)
+        if t is None:
+            continue
+        stamped += 1
+        first_ts = t if first_ts is None else first_ts
+        end = t
+        g = per.get(sig)
+        if g is None:
+            per[sig] = {"lines": 1, "beats": 0, "back": 0, "sum": 0, "min": None, "max": -1, "from": -1, "to": -1,
+                        "to_ts": 0, "first": i, "last": i, "last_ts": t, "hist": [0] * PAUSE_BUCKETS}
+            continue
+        beat = t - g["last_ts"]
+        g["lines"] += 1
+        if beat < 0:
+            g["back"] += 1
+        else:
+            g["beats"] += 1
+            g["sum"] += beat
+            g["min"] = beat if g["min"] is None else min(g["min"], beat)
+            g["hist"][pause_bucket(beat)] += 1
+            if beat > g["max"]:
+                g["max"], g["from"], g["to"], g["to_ts"] = beat, g["last"], i, t
+        g["last"], g["last_ts"] = i, t
+    out = cadence_head(len(raws), stamped, len(seen), first_ts, end)
+    listed = []
+    for sig, g in per.items():
+        j = cadence_judge(g["beats"], g["sum"], g["max"], g["last_ts"], end, g["hist"], min_ms, ratio, min_count, min_reg)
+        if j is None:
+            continue
+        out["periodic"] += 1
+        out["missed"] += j["missed"]
+        out["stopped"] += j["stopped"]
+        if cadence_listed(kind, j["missed"], j["stopped"]):
+            listed.append((cadence_order_key(order, j["typicalMs"], g["max"], j["overdueMs"], g["beats"], g["first"]),
+                           (sig, g["lines"], g["beats"], g["back"], g["sum"], g["min"], g["max"], g["from"], g["to"],
+                            g["to_ts"], g["first"], g["last"], g["last_ts"], g["hist"], j, raws[g["first"]])))
+    listed.sort(key=lambda kv: kv[0])
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    out["top"] = [cadence_row(*row) for _, row in listed]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Trace report (an extra, as the gap report): which stack traces does a log hold, how often, where
 # first, with which root cause, and does any pattern explain them? These functions are the
 # specification of ``log_parser_amd/traces.py`` and of the line classifier and the run scan

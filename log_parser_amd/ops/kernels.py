@@ -1472,6 +1472,102 @@ def pause_scan(ts: torch.Tensor, sig: torch.Tensor, min_ms: int, line_base: int 
     return rows, stats, hist, (None if n_ts == TS_NONE else (n_ts, n_line, n_sig))
 
 
+CD_TILE = 2048              # lines per block of k_cd_tile (csrc/kernels/cadence.hip)
+CDL_ROWS = 256              # rows per block of k_cdl_tiles / k_cdl_emit
+# columns of a cadence state (csrc/kernels/lp_api.h)
+(CD_SIG, CD_LINES, CD_BEATS, CD_BACKWARD, CD_SUM, CD_MIN, CD_MAX, CD_MAX_FROM, CD_MAX_TO, CD_FIRST_LINE, CD_LAST_LINE,
+ CD_LAST_TS, CD_FIRST_TS, CD_MAX_TO_TS) = range(14)
+CD_COLS = 14
+
+
+def beat_state(device) -> torch.Tensor:
+    """The cadence state of no line at all."""
+    return torch.empty((CD_COLS, 0), dtype=torch.int64, device=device)
+
+
+def beat_scan(ts: torch.Tensor, sig: torch.Tensor, line_base: int = 0, state: Optional[torch.Tensor] = None,
+              cap: Optional[int] = None):
+    """Per stamped line the *beat* since the previous stamped line of the same template, and the
+    templates' running rows (``ts`` / ``sig``: int64[L], what ``line_stamps`` gives; line i has the
+    global number ``line_base + i``). ``state``: None, or what an earlier call returned for the
+    lines before ``line_base``. Returns
+
+    * beat int64[L]: the line's stamp minus the stamp of the previous stamped line of its
+      signature -- in this run or, through ``state``, before it; ``TS_NONE`` for an unstamped line
+      and for the first stamped line of a signature;
+    * bkt int64[L]: the bit length of a beat >= 0 (``golden.pause_bucket``), else ``TS_NONE`` --
+      the ``eff`` column of ``CellTable.fold(sig, bkt, line_base, 1)``;
+    * the new state int64[CD_COLS, T]: one row per signature seen so far, sorted by signature (as
+      a signed number); columns ``CD_SIG .. CD_MAX_TO_TS``. The state after runs A then B is the
+      state of the one run A + B, bit for bit.
+
+    k_cd_tile writes one row per (tile of 2,048 lines, signature) with the capacity protocol of
+    ``novel_lines`` (``cap``: rows of the first try); state rows and tile rows are sorted by first
+    line, then stably by signature, with torch; k_cdl_tiles / k_cdl_prefix / k_cdl_emit join the
+    rows of a signature in that order and write the beats across tile and run borders. CPU: the
+    host twins. The row counts are the two small reads."""
+    dev = ts.device
+    if ts.dtype != torch.int64 or not ts.is_contiguous() or ts.dim() != 1:
+        raise ValueError("beat_scan: ts must be contiguous int64[L]")
+    L = ts.numel()
+    if sig.dtype != torch.int64 or sig.dim() != 1 or sig.numel() != L or not sig.is_contiguous() or sig.device != dev:
+        raise ValueError("beat_scan: sig must be contiguous int64[L] on the device of ts")
+    if isinstance(line_base, bool) or not isinstance(line_base, int) or not 0 <= line_base <= I64_MAX - L:
+        raise ValueError("beat_scan: line_base out of range")
+    if state is None:
+        state = beat_state(dev)
+    elif (not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.dim() != 2
+          or state.shape[0] != CD_COLS or not state.is_contiguous() or state.device != dev):
+        raise ValueError("beat_scan: state must be contiguous int64[%d, T] on the device of ts" % CD_COLS)
+    if state.shape[1] and line_base == 0:
+        raise ValueError("beat_scan: a state speaks of lines before line_base")
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 0):
+        raise ValueError("beat_scan: cap must be None or an integer >= 0")
+    beat = torch.empty(L, dtype=torch.int64, device=dev)
+    bkt = torch.empty(L, dtype=torch.int64, device=dev)
+    if L == 0:
+        return beat, bkt, state
+    rows = beat_tile_rows(ts, sig, line_base, beat, bkt, cap)
+    rows = beat_sort_rows(torch.cat([state, rows], dim=1))
+    return beat, bkt, beat_link_rows(rows, line_base, beat, bkt)
+
+
+def beat_tile_rows(ts, sig, line_base: int, beat, bkt, cap: Optional[int] = None) -> torch.Tensor:
+    """First step of ``beat_scan`` (its checks made): k_cd_tile. Writes ``beat`` / ``bkt`` inside
+    the tiles and returns the tile rows int64[CD_COLS, n]; the read of n is the capacity protocol."""
+    L, dev = ts.numel(), ts.device
+    cap = min(L, max(1024, L // 4)) if cap is None else cap
+    while True:
+        rows = torch.empty((CD_COLS, max(cap, 1)), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        N.cadence_tile(ts.data_ptr(), sig.data_ptr(), L, line_base, beat.data_ptr(), bkt.data_ptr(), rows.data_ptr(),
+                       cap, cnt.data_ptr(), _s(ts), ts.is_cuda)
+        n = int(cnt.item())
+        if n <= cap:
+            return rows[:, :n]
+        cap = n
+
+
+def beat_sort_rows(rows: torch.Tensor) -> torch.Tensor:
+    """Second step: the rows by (signature, first line). A state row lies before line_base and
+    leads its group. The sorts wipe the order the block atomics gave the tile rows."""
+    o = torch.sort(rows[CD_FIRST_LINE], stable=True)[1]
+    o = o[torch.sort(rows[CD_SIG][o], stable=True)[1]]
+    return rows[:, o].contiguous()
+
+
+def beat_link_rows(rows: torch.Tensor, line_base: int, beat, bkt) -> torch.Tensor:
+    """Third step: k_cdl_tiles / k_cdl_prefix / k_cdl_emit over the sorted rows. Writes the beats
+    across tile and run borders and returns the new state; the read of its row count."""
+    dev, R, L = rows.device, rows.shape[1], beat.numel()
+    out = torch.empty((CD_COLS, max(R, 1)), dtype=torch.int64, device=dev)
+    head = torch.empty(1, dtype=torch.int64, device=dev)
+    tmp = torch.empty(N.cadence_link_tmp_words(R), dtype=torch.int64, device=dev) if rows.is_cuda else None
+    N.cadence_link(rows.data_ptr(), R, out.data_ptr(), max(R, 1), head.data_ptr(), _p(tmp), line_base, L,
+                   beat.data_ptr(), bkt.data_ptr(), _s(rows), rows.is_cuda)
+    return out[:, :int(head.item())].contiguous()
+
+
 def timeline_hist(eff: torch.Tensor, feat: torch.Tensor, ev_line: torch.Tensor, ev_pat: torch.Tensor,
                   sev_index: torch.Tensor, t0: int, W: int, nb: int, S: int) -> torch.Tensor:
     """int64[nb, 3 + S]: per bucket ``[t0 + b * W, t0 + (b + 1) * W)`` the lines whose effective

@@ -505,6 +505,71 @@ def pause_log(n_lines: int, templates: List[str], seed: int = 0, pauses: int = 6
     return "".join(parts), sorted(planted, reverse=True)
 
 
+CADENCE_HOLE = "INFO  [watchdog] fed the watchdog, tick %d"                  # every 5 s, with one hole
+CADENCE_STOPPED = "INFO  [lease] renewed the leader lease, term %d"          # every 30 s, until it stops
+CADENCE_STEADY = "DEBUG [health] liveness probe answered, check %d"          # every 12 s, all the way
+CADENCE_HOLE_MS = 90_000
+
+
+def cadence_log(n_lines: int, templates: List[str], seed: int = 0) -> Tuple[str, Dict[str, dict]]:
+    """A log with three periodic lines among a bulk that is not. Stamped lines follow each other by
+    1..400 ms (the clock of ``pause_log``); about 3 % of the lines are unstamped ``\\tat ...``
+    frames; the bulk is ``templates`` (``log_templates``) with the skewed weights of
+    ``templated_log``. A plant takes the place of a bulk line when its next beat is due: the
+    ``CADENCE_HOLE`` line every 5 s +- 10 %, except that at two fifths of the log its next beat
+    comes ``CADENCE_HOLE_MS`` late (once); the ``CADENCE_STOPPED`` line every 30 s +- 10 % and never
+    from line ``11 * n_lines // 20`` on; the ``CADENCE_STEADY`` line every 12 s +- 10 % to the
+    end. Returns (text, {"hole" | "stopped" | "steady": the plant's numbers}) -- ``template``,
+    ``lines``, ``beats``, ``sumMs``, ``maxMs``, ``fromLine``, ``toLine`` (of the first largest
+    beat), ``typicalMs``, ``missedBeats``, ``firstLine``, ``lastLine`` and ``lastMs`` (its last
+    stamp); lines 0-based, all known by construction."""
+    rng = random.Random(seed)
+    weights = [1.0 / (k + 1) for k in range(len(templates))]
+    epoch = datetime(1970, 1, 1)
+    t = TREND_T0_MS
+    plants = [{"name": "hole", "text": CADENCE_HOLE, "period": 5000, "due": t + 2500, "at": []},
+              {"name": "stopped", "text": CADENCE_STOPPED, "period": 30000, "due": t + 4000, "at": []},
+              {"name": "steady", "text": CADENCE_STEADY, "period": 12000, "due": t + 7000, "at": []}]
+    hole_line, stop_line = 2 * n_lines // 5, 11 * n_lines // 20
+    holed = False
+    parts: List[str] = []
+    bulk = iter(rng.choices(templates, weights=weights, k=n_lines))
+    for i in range(n_lines):
+        body = next(bulk).split(" ", 1)[1]      # (behind the template's own stamp)
+        if i and rng.random() < 0.03:
+            parts.append("\tat com.example.worker.Task.run(Task.java:%d)\n" % rng.randrange(10, 400))
+            continue
+        t += rng.randrange(1, 401)
+        if i >= hole_line and not holed:
+            plants[0]["due"] += CADENCE_HOLE_MS
+            holed = True
+        due = [p for p in plants if t >= p["due"] and not (p["name"] == "stopped" and i >= stop_line)]
+        if due:
+            p = due[0]
+            line = p["text"] % len(p["at"])
+            p["at"].append((i, t))
+            p["due"] = t + p["period"] * rng.randrange(90, 111) // 100
+        else:
+            line = body % tuple(rng.randrange(1, 1 << 20) for _ in range(body.count("%")))
+        d = epoch + timedelta(milliseconds=t)
+        parts.append("%04d-%02d-%02dT%02d:%02d:%02d.%03dZ %s\n" % (d.year, d.month, d.day, d.hour, d.minute, d.second,
+                                                                  d.microsecond // 1000, line))
+    known: Dict[str, dict] = {}
+    for p in plants:
+        at = p["at"]
+        beats = [(b[1] - a[1], a[0], b[0]) for a, b in zip(at, at[1:])]
+        row = {"template": p["text"], "lines": len(at), "beats": len(beats), "firstLine": at[0][0] if at else None,
+               "lastLine": at[-1][0] if at else None, "lastMs": at[-1][1] if at else None}
+        if len(beats) >= 2:
+            mx = max(beats, key=lambda b: (b[0], -b[2]))
+            total = sum(b[0] for b in beats)
+            typical = (total - mx[0]) // (len(beats) - 1)
+            row.update({"sumMs": total, "maxMs": mx[0], "fromLine": mx[1], "toLine": mx[2], "typicalMs": typical,
+                        "missedBeats": mx[0] // typical - 1})
+        known[p["name"]] = row
+    return "".join(parts), known
+
+
 CORRELATED_FAIL ="request aborted: upstream deadline exceeded"     # what the last line of a failing request says
 
 
