@@ -109,6 +109,36 @@ static CellTab ct_from(const py::tuple& t) {
   return T;
 }
 
+// (key, field, value, count, first, last, used, cap) of a value table (var_table.h)
+static VarTab vt_from(const py::tuple& t) {
+  VarTab T;
+  T.key = P<int64_t>(t[0].cast<uint64_t>());
+  T.field = P<int64_t>(t[1].cast<uint64_t>());
+  T.value = P<int64_t>(t[2].cast<uint64_t>());
+  T.count = P<unsigned long long>(t[3].cast<uint64_t>());
+  T.first = P<long long>(t[4].cast<uint64_t>());
+  T.last = P<long long>(t[5].cast<uint64_t>());
+  T.used = P<unsigned long long>(t[6].cast<uint64_t>());
+  T.cap = t[7].cast<int64_t>();
+  return T;
+}
+
+// (field, value, count, first, last) row columns
+static VarRows vw_from(const py::tuple& t) {
+  VarRows R;
+  R.field = P<int64_t>(t[0].cast<uint64_t>());
+  R.value = P<int64_t>(t[1].cast<uint64_t>());
+  R.count = P<int64_t>(t[2].cast<uint64_t>());
+  R.first = P<int64_t>(t[3].cast<uint64_t>());
+  R.last = P<int64_t>(t[4].cast<uint64_t>());
+  return R;
+}
+
+// a GapTab used as a set, or None: the empty set
+static GapTab gt_from_opt(const py::object& o) {
+  return o.is_none() ? GapTab{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0} : gt_from(o.cast<py::tuple>());
+}
+
 // (sig, bucket, count, first) row columns
 static CellRows cr_from(const py::tuple& t) {
   CellRows R;
@@ -1272,6 +1302,71 @@ PYBIND11_MODULE(_lpnative, m) {
         py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sig"),
         py::arg("out_line"), py::arg("out_key"), py::arg("out_val"), py::arg("cap"), py::arg("cnt"),
         py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  // ---- variants report (variants.hip): the value hashes of every line's fields, the value table
+  m.def("line_vars", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, uint64_t sig,
+                        uint64_t out_line, uint64_t out_field, uint64_t out_value, int64_t cap, uint64_t cnt, uint64_t s,
+                        bool dev, int per_block) {
+    VarLinesArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.nl = nl;
+    A.sig = P<int64_t>(sig);
+    A.out_line = P<int32_t>(out_line); A.out_field = P<int64_t>(out_field); A.out_value = P<int64_t>(out_value);
+    A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    if (dev) {
+      line_vars_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    line_vars_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("sig"),
+        py::arg("out_line"), py::arg("out_field"), py::arg("out_value"), py::arg("cap"), py::arg("cnt"),
+        py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  m.def("var_fold", [](py::tuple tab, py::object skip, uint64_t field, uint64_t value, uint64_t ord, int64_t n, uint64_t s,
+                       bool dev, int tile) {
+    const VarTab T = vt_from(tab);
+    const GapTab S = gt_from_opt(skip);
+    if (dev) {
+      var_fold_dev(T, S, P<const int64_t>(field), P<const int64_t>(value), P<const int64_t>(ord), n, s, tile);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    var_fold_host(T, S, P<const int64_t>(field), P<const int64_t>(value), P<const int64_t>(ord), n); },
+        py::arg("tab"), py::arg("skip"), py::arg("field"), py::arg("value"), py::arg("ord"), py::arg("n"),
+        py::arg("stream"), py::arg("dev"), py::arg("tile") = 0);
+  m.def("var_rows", [](py::tuple tab, py::tuple rows, int64_t out_cap, uint64_t cnt, uint64_t s, bool dev) {
+    const VarTab T = vt_from(tab);
+    const VarRows R = vw_from(rows);
+    if (dev) {
+      var_rows_dev(T, R, out_cap, P<unsigned long long>(cnt), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    var_rows_host(T, R, out_cap, P<unsigned long long>(cnt)); },
+        py::arg("tab"), py::arg("rows"), py::arg("out_cap"), py::arg("cnt"), py::arg("stream"), py::arg("dev"));
+  m.def("var_reinsert", [](py::tuple tab, py::tuple rows, int64_t n, uint64_t s, bool dev) {
+    const VarTab T = vt_from(tab);
+    const VarRows R = vw_from(rows);
+    if (dev) {
+      var_reinsert_dev(T, R, n, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    var_reinsert_host(T, R, n); },
+        py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
+  m.def("var_winners", [](py::tuple tab, uint64_t field, uint64_t value, uint64_t ord, int64_t n, uint64_t out, uint64_t cnt,
+                          uint64_t s, bool dev) {
+    const VarTab T = vt_from(tab);
+    if (dev) {
+      var_winners_dev(T, P<const int64_t>(field), P<const int64_t>(value), P<const int64_t>(ord), n, P<int64_t>(out),
+                      P<unsigned long long>(cnt), s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    var_winners_host(T, P<const int64_t>(field), P<const int64_t>(value), P<const int64_t>(ord), n, P<int64_t>(out),
+                     P<unsigned long long>(cnt)); },
+        py::arg("tab"), py::arg("field"), py::arg("value"), py::arg("ord"), py::arg("n"), py::arg("out"), py::arg("cnt"),
+        py::arg("stream"), py::arg("dev"));
   // ---- trends report (trends.hip): stamp and signature of every line, the cell table
   m.def("line_stamps", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, uint64_t sig, uint64_t ts,
                           uint64_t s, bool dev, int per_block) {

@@ -522,6 +522,54 @@ void line_vals_dev(const ValLinesArgs& A, uint64_t stream, int per_block = 0);
 void line_vals_host(const ValLinesArgs& A);
 }  // namespace lp
 
+// ---- variants report (variants.hip): the value hashes of every line's fields, counts per (field, value)
+#include "var_table.h"
+namespace lp {
+struct VarLinesArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t nl;                // lines of ls / ll, at most 2^31 - 1: every one is walked
+  // outputs: sig[i] = template signature of line i (gaps_core.h); the first 8 fields of every line
+  // (var_core.h) as (line number, val_key(signature, field), hash of the token) triples, the first
+  // `cap` of them; cnt[0] += triples (all of them: above cap the caller re-runs, as with
+  // line_vals_dev), cnt[1] += lines with at least one field
+  int64_t* sig;
+  int32_t* out_line; int64_t* out_field; int64_t* out_value;
+  int64_t cap;
+  unsigned long long* cnt;   // [2], zeroed by the caller
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from nl.
+// GPU: the triples come in no particular order
+void line_vars_dev(const VarLinesArgs& A, uint64_t stream, int per_block = 0);
+// appends in line order, the fields of a line in byte order
+void line_vars_host(const VarLinesArgs& A);
+struct VarRows {             // rows of a value table, or the rows to put into one
+  int64_t* field; int64_t* value; int64_t* count; int64_t* first; int64_t* last;
+};
+// n triples (field[i], value[i], ord[i]: the global line number) into the table: per (field, value)
+// the number of triples, the smallest and the largest ordinal. A triple whose field `skip` holds
+// (a GapTab used as a set; key == nullptr: the empty set) is dropped. The caller keeps
+// 2 * (used + n) <= cap. tile: triples per block (256..2048, a multiple of 256), 0: chosen from n
+void var_fold_dev(const VarTab& T, const GapTab& skip, const int64_t* field, const int64_t* value, const int64_t* ord,
+                  int64_t n, uint64_t stream, int tile = 0);
+// the occupied slots as rows, in no particular order: the first out_cap of them; *cnt += all of them
+void var_rows_dev(const VarTab& T, const VarRows& R, int64_t out_cap, unsigned long long* cnt, uint64_t stream);
+// n rows of distinct (field, value) into a table that holds none of them (growth, purge); used[0] is
+// left to the caller, who knows it is n
+void var_reinsert_dev(const VarTab& T, const VarRows& R, int64_t n, uint64_t stream);
+// out[*cnt ...] = i for every triple whose (field, value) the table holds with first == ord[i] (out
+// holds n entries; *cnt grows by the number appended)
+void var_winners_dev(const VarTab& T, const int64_t* field, const int64_t* value, const int64_t* ord, int64_t n,
+                     int64_t* out, unsigned long long* cnt, uint64_t stream);
+void var_fold_host(const VarTab& T, const GapTab& skip, const int64_t* field, const int64_t* value, const int64_t* ord,
+                   int64_t n);
+void var_rows_host(const VarTab& T, const VarRows& R, int64_t out_cap, unsigned long long* cnt);
+void var_reinsert_host(const VarTab& T, const VarRows& R, int64_t n);
+void var_winners_host(const VarTab& T, const int64_t* field, const int64_t* value, const int64_t* ord, int64_t n,
+                      int64_t* out, unsigned long long* cnt);
+}  // namespace lp
+
 // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
 namespace lp {
 // out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN

@@ -1,4 +1,4 @@
-// Block primitives of the report kernels (gaps, gap_table, novelty, leadup, correlate, values,
+// Block primitives of the report kernels (gaps, gap_table, novelty, leadup, correlate, values, variants,
 // timeline, trends, pauses, cadence, traces): the scans, the compaction steps and the launch geometry that
 // every "one lane per line and round" kernel needs, written once. Every device piece is for blocks
 // of 256 lanes (four waves of 64) and is called by ALL lanes of the block -- shuffles, ballots and

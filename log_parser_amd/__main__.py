@@ -41,6 +41,13 @@
                                                the numeric fields of the line templates of a log:
                                                count, sum, min, max, and the line of the largest
                                                value -- the fields that peak first (JSON)
+  variants  FILE... [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--max-distinct N]
+            [--order odd|count|distinct|first] [--min-count N] [--min-fill F] [--all] [--show N]
+            [--top N]
+                                               the values that the variable tokens of the line
+                                               templates take: how often, where first and last, the
+                                               field with one deviant among thousands first; several
+                                               files continue ONE log (JSON)
   trends    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--bucket S]
             [--at T|first-event|first-error] [--ratio R] [--min-count N] [--kind K] [--order O]
             [--top N]
@@ -235,6 +242,27 @@ def cmd_values(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_variants(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    try:
+        acc = lp.variant_accumulator(args.max_distinct)
+        for path in args.files:             # several files continue ONE log
+            if args.stream:
+                from .api import _source
+                with _source(path) as src:
+                    acc.add_stream(src, args.chunk_bytes)
+            else:
+                with open(path, "rb") as f:
+                    acc.add_document(f.read())
+        rep = acc.report(top=args.top, order=args.order, min_count=args.min_count, min_fill=args.min_fill,
+                         varying=not args.all, show=args.show)
+    except ValueError as e:                 # a count, a share or the limit of distinct values out of range
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def cmd_trends(args, cfg: Config) -> int:
     lp = _parser(args, cfg)
     at = int(args.at) if args.at is not None and args.at.lstrip("-").isdigit() else args.at
@@ -378,6 +406,24 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="list only the fields with a value on at least this share of their template's lines "
                         "(default 0.9)")
     v.add_argument("--all-fields", action="store_true", help="list the fields whose value never changes too")
+    w = sub.add_parser("variants", help="the values that the variable tokens of the line templates of a log take")
+    w.add_argument("files", nargs="+", metavar="FILE")
+    _library_options(w)
+    w.add_argument("--stream", action="store_true", help="the files processed in chunks (same report)")
+    w.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    w.add_argument("--max-distinct", type=int, default=64, metavar="N",
+                   help="a field with more than N distinct values is only counted (2..4096, default 64)")
+    w.add_argument("--order", choices=("odd", "count", "distinct", "first"), default="odd",
+                   help="smallest share of lines off the most common value first (default), most tokens first, most "
+                        "distinct values first, or in order of first appearance")
+    w.add_argument("--min-count", type=int, default=5, metavar="N",
+                   help="list only the fields with at least N tokens (default 5)")
+    w.add_argument("--min-fill", type=float, default=0.9, metavar="F",
+                   help="list only the fields present on at least this share of their template's lines (default 0.9)")
+    w.add_argument("--all", action="store_true", help="list the fields whose value never changes too")
+    w.add_argument("--show", type=int, default=5, metavar="N",
+                   help="values listed per field: all up to 2N, else the N most and the N least common (default 5)")
+    w.add_argument("--top", type=int, default=20, help="fields reported (default 20)")
     d = sub.add_parser("trends", help="line templates of a log file that started, stopped, surged or faded over its time")
     d.add_argument("file")
     _library_options(d)
@@ -438,6 +484,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
             "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values,
+            "variants": cmd_variants,
             "trends": cmd_trends, "pauses": cmd_pauses, "cadence": cmd_cadence}[args.cmd](args, cfg)
 
 

@@ -41,6 +41,7 @@ SOURCES = [
     ("kernels/leadup.hip", "hip"),
     ("kernels/correlate.hip", "hip"),
     ("kernels/values.hip", "hip"),
+    ("kernels/variants.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("kernels/trends.hip", "hip"),
     ("kernels/pauses.hip", "hip"),

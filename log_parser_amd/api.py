@@ -40,6 +40,11 @@ to embedders, with what an in-process user needs beyond one call at a time:
   min, max and where the largest value is -- ``golden.values``; ``values_stream`` /
   ``values_resident`` for one log too large for one piece, ``value_accumulator`` for a log that
   arrives over time;
+* ``variants`` / ``variants_file``: the values that the variable tokens of the line templates of
+  a log take -- per template and field its distinct tokens with count, first and last line, the
+  field with one deviant among thousands first -- ``golden.variants``; ``variants_stream`` /
+  ``variants_resident`` for one log too large for one piece, ``variant_accumulator`` for a log
+  that arrives over time;
 * ``trends`` / ``trends_file``: the line templates of a log that started, stopped, surged or
   faded across a pivot in its own time -- ``golden.trends``; ``trends_stream`` /
   ``trends_resident`` for one log too large for one piece, ``trend_accumulator`` for a log that
@@ -479,6 +484,66 @@ class LogParser:
                         min_fill: float = 0.9, varying: bool = True) -> dict:
         """``values`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
         return self.values_stream(resident, None, top, order, min_count, min_fill, varying)
+
+    # ---- variants report ---------------------------------------------------------------------
+    def variants(self, logs, max_distinct: int = 64, top: Optional[int] = 20, order: str = "odd", min_count: int = 5,
+                 min_fill: float = 0.9, varying: bool = True, show: int = 5) -> dict:
+        """Which values do the variable tokens of the line templates of one document (str or
+        bytes) take, how often, and which is the odd one out? The fields are those of ``values``
+        (the digit-holding tokens of a line behind its stamp, the first 8), counted whether or not
+        they read as numbers; a value is the token as it is. A field with at most ``max_distinct``
+        (2..4096) values over the whole log is listed with ``count``, ``lines``, ``fill``,
+        ``distinct``, ``odd`` (its lines that do not hold the most common value), ``oddShare`` and
+        its ``values`` -- all of them up to ``2 * show``, else the ``show`` most and least common
+        -- each with ``token``, ``count``, ``share``, ``firstLine``, ``lastLine``; a field with more
+        (an id, a counter) is only counted in ``unboundedFields``. Listed are the fields with
+        ``count >= min_count``, ``count >= min_fill * lines`` and, with ``varying``, more than one
+        value. ``order="odd"``: the smallest ``oddShare`` first; ``"count"``; ``"distinct"``;
+        ``"first"``; ``top=None``: every field. No pattern takes part. ``Engine.variants_bytes``;
+        ``golden.variants`` is the specification; the frequency window is not touched."""
+        from .variants import check_args
+        check_args(max_distinct, order, min_count, min_fill, show)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("variants"):
+            return self.engine.variants_bytes(logs, max_distinct=max_distinct, top=top, order=order,
+                                              min_count=min_count, min_fill=min_fill, varying=varying, show=show)
+
+    def variants_file(self, path: str, max_distinct: int = 64, top: Optional[int] = 20, order: str = "odd",
+                      min_count: int = 5, min_fill: float = 0.9, varying: bool = True, show: int = 5) -> dict:
+        """``variants`` of a log file, read as ONE document whatever its size."""
+        from .variants import check_args
+        check_args(max_distinct, order, min_count, min_fill, show)
+        with open(path, "rb") as f:
+            return self.variants(f.read(), max_distinct, top, order, min_count, min_fill, varying, show)
+
+    def variant_accumulator(self, max_distinct: int = 64, line_base: int = 0):
+        """A ``variants.VariantAccumulator`` on this parser's engine for a log that arrives over
+        time (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then
+        ``report``); each of its calls runs under the batcher guard and the lock of ``variants``.
+        ``max_distinct`` is fixed here."""
+        from .variants import VariantAccumulator
+        with self._engine_guard("variants"):
+            return VariantAccumulator(self.engine, max_distinct, guard=lambda: self._engine_guard("variants"),
+                                      line_base=line_base)
+
+    def variants_stream(self, src_or_path, chunk_bytes: Optional[int] = None, max_distinct: int = 64,
+                        top: Optional[int] = 20, order: str = "odd", min_count: int = 5, min_fill: float = 0.9,
+                        varying: bool = True, show: int = 5) -> dict:
+        """``variants`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). Exactly the
+        one-document report, whatever the chunk size (variants.py says why)."""
+        from .variants import check_args
+        check_args(max_distinct, order, min_count, min_fill, show)
+        acc = self.variant_accumulator(max_distinct)
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(top, order, min_count, min_fill, varying, show)
+
+    def variants_resident(self, resident, max_distinct: int = 64, top: Optional[int] = 20, order: str = "odd",
+                          min_count: int = 5, min_fill: float = 0.9, varying: bool = True, show: int = 5) -> dict:
+        """``variants`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        return self.variants_stream(resident, None, max_distinct, top, order, min_count, min_fill, varying, show)
 
     # ---- trends report -----------------------------------------------------------------------
     def trends(self, logs, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,

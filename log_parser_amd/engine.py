@@ -903,6 +903,15 @@ class Engine:
         from .values import values_document
         return values_document(self, bytes(data), top, order, min_count, min_fill, varying)
 
+    # ------------------------------------------------------------------ variants report
+    def variants_bytes(self, data: bytes, max_distinct: int = 64, top: Optional[int] = 20, order: str = "odd",
+                       min_count: int = 5, min_fill: float = 0.9, varying: bool = True, show: int = 5) -> dict:
+        """Which values do the variable tokens of one document's line templates take, and which is
+        the odd one out? (variants.py; ``golden.variants`` is the specification.) The matchers do
+        not run, nothing is scored and the frequency window is not touched."""
+        from .variants import variants_document
+        return variants_document(self, bytes(data), max_distinct, top, order, min_count, min_fill, varying, show)
+
     # ------------------------------------------------------------------ trends report
     def trends_bytes(self, data: bytes, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
                      kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,

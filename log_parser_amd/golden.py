@@ -930,6 +930,161 @@ def values(logs, top: Optional[int] = 20, order: str = "peak", min_count: int = 
 
 
 # ---------------------------------------------------------------------------------------------
+# Variants report (an extra, as the gap report): the categorical sibling of the values report. Which
+# values does a template's variable token take, how often, and which value is the odd one out --
+# the one 503 among ten thousand 200s? The fields and their numbering are ``line_fields``', the
+# group key is ``val_key``; a field counts whether or not it reads as a number, and its value is the
+# token itself, compared through ``var_hash``. These functions are the specification of
+# ``log_parser_amd/variants.py`` and of the kernels (csrc/kernels/var_core.h, var_table.h,
+# variants.hip).
+#
+# Known limits: the limits of ``line_fields`` (the first ``SIG_MAX_BYTES`` bytes of a line, its
+# first ``VAL_PER_LINE`` fields, only the stamps of ``line_timestamp`` are skipped); a token cut at
+# byte ``SIG_MAX_BYTES`` is the value its first part spells; case is kept, so ``0xAB`` and ``0xab``
+# are two values; two tokens may share a 64-bit hash, two (template, field) pairs a 64-bit key, and
+# two (field, value) pairs that share the 64-bit ``var_cell_key`` are ONE value; a field with more
+# than ``max_distinct`` values is only counted, never listed.
+
+VARIANT_ORDERS = ("odd", "count", "distinct", "first")
+VAR_MIN_DISTINCT, VAR_MAX_DISTINCT = 2, 4096
+
+
+def var_hash(token: bytes) -> int:
+    """FNV-1a-64 of the token's bytes as they are (case kept)."""
+    h = _FNV_OFFSET
+    for c in bytes(token):
+        h = ((h ^ c) * _FNV_PRIME) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def var_cell_key(field: int, value: int) -> int:
+    """The 64-bit table key of (``val_key`` of the field, ``var_hash`` of the token):
+    ``trend_cell_key``'s mix."""
+    return (field + value * _TREND_MIX) & _U64
+
+
+def variants_check_args(max_distinct: int = 64, order: str = "odd", min_count: int = 5, min_fill: float = 0.9,
+                        show: int = 5) -> None:
+    if (isinstance(max_distinct, bool) or not isinstance(max_distinct, int)
+            or not VAR_MIN_DISTINCT <= max_distinct <= VAR_MAX_DISTINCT):
+        raise ValueError("max_distinct must be an integer in [%d, %d]" % (VAR_MIN_DISTINCT, VAR_MAX_DISTINCT))
+    if order not in VARIANT_ORDERS:
+        raise ValueError("order must be 'odd', 'count', 'distinct' or 'first'")
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+        raise ValueError("min_count must be an integer >= 1")
+    if isinstance(min_fill, bool) or not isinstance(min_fill, (int, float)) or not 0.0 <= min_fill <= 1.0:
+        raise ValueError("min_fill must be in [0, 1]")
+    if isinstance(show, bool) or not isinstance(show, int) or show < 1:
+        raise ValueError("show must be an integer >= 1")
+
+
+def variants_order_key(order: str, sig: int, j: int, count: int, odd: int, distinct: int, first: int):
+    """The sort key of a group: exact arithmetic (ints and ``Fraction``), ``sig`` unsigned."""
+    if order == "odd":
+        return (Fraction(odd, count), -count, first, sig, j)
+    if order == "count":
+        return (-count, first, sig, j)
+    if order == "distinct":
+        return (-distinct, first, sig, j)
+    return (first, j)
+
+
+def variants_listed(values: list, show: int) -> list:
+    """``values``: (count, first line, ...) tuples of a group. Sorted by (-count, first line); all
+    of them when there are at most ``2 * show``, else the ``show`` most and the ``show`` least
+    common."""
+    values = sorted(values, key=lambda v: (-v[0], v[1]))
+    return values if len(values) <= 2 * show else values[:show] + values[-show:]
+
+
+def variants_value(sig: int, j: int, value: int, count: int, total: int, first: int, last: int, raw: bytes) -> dict:
+    """One listed value from its numbers (lines 0-based) and its own first line: ValueError unless
+    that line has the template ``sig`` and field ``j`` of it hashes to ``value``."""
+    fields = line_fields(raw)
+    if line_signature(raw) != sig or j >= len(fields) or var_hash(fields[j][2]) != value or not first <= last:
+        raise ValueError("variants: line %d does not hold field %d of %016x with the value %016x"
+                         % (first + 1, j, sig, value))
+    return {"token": fields[j][2].decode("ascii"), "count": count, "share": count / total,
+            "firstLine": first + 1, "lastLine": last + 1}
+
+
+def variants_row(sig: int, j: int, lines: int, values: list, show: int) -> dict:
+    """One row of the report. ``values``: (count, first line, last line, hash, raw first line) of
+    every value of the group (lines 0-based)."""
+    count = sum(v[0] for v in values)
+    ordered = sorted(values, key=lambda v: (-v[0], v[1]))
+    odd = count - ordered[0][0]
+    first = min(values, key=lambda v: v[1])
+    return {"signature": "%016x" % sig, "field": j, "count": count, "lines": lines, "fill": count / lines,
+            "distinct": len(values), "odd": odd, "oddShare": odd / count, "firstLine": first[1] + 1,
+            "template": line_template(first[4]).decode("utf-8", errors="replace"),
+            "example": first[4].decode("utf-8", errors="replace"),
+            "values": [variants_value(sig, j, h, c, count, f, l, raw)
+                       for c, f, l, h, raw in variants_listed(values, show)]}
+
+
+def variants_head(total: int, field_lines: int, tokens: int, templates: int, fields: int, unbounded: int,
+                  max_distinct: int) -> dict:
+    return {"totalLines": total, "fieldLines": field_lines, "tokens": tokens, "templates": templates,
+            "fields": fields, "unboundedFields": unbounded, "maxDistinct": max_distinct, "top": []}
+
+
+def variants(logs, max_distinct: int = 64, top: Optional[int] = 20, order: str = "odd", min_count: int = 5,
+             min_fill: float = 0.9, varying: bool = True, show: int = 5) -> dict:
+    """The variants report of ``logs`` (str or bytes; no pattern takes part). A *group* is
+    (template signature of the line, field number j) of ``line_fields``; a *value* of it is a
+    token, by ``var_hash``. Per value: its lines (``count``), the first and the last of them. A
+    group with at most ``max_distinct`` distinct values over the whole log is *enumerable* and is
+    reported; one with more (an id, a counter, a duration) is *unbounded* and only counted in
+    ``unboundedFields``. Per group: ``count`` (the sum over its values), ``lines`` (all lines of
+    the template), ``fill`` = count / lines, ``distinct``, ``odd`` = count minus the count of the
+    most common value, ``oddShare`` = odd / count, ``firstLine`` (the smallest first line of its
+    values) with its ``template`` and ``example``, and ``values``: sorted by (-count, first line),
+    all of them when ``distinct <= 2 * show``, else the ``show`` most and the ``show`` least
+    common; each with its ``token`` (from its own first line), ``count``, ``share`` = count /
+    group count, ``firstLine``, ``lastLine``. Dropped are the groups with ``count < min_count``,
+    those with ``count < min_fill * lines`` and, with ``varying``, those with one value.
+    ``order="odd"``: by (odd / count, -count, first line, signature, field) -- the field with one
+    deviant among ten thousand first; ``"count"``: (-count, first line, signature, field);
+    ``"distinct"``: (-distinct, ...); ``"first"``: (first line, field). ``tokens`` counts all
+    fields of all lines, ``fieldLines`` the lines with at least one, ``templates`` the templates
+    of all lines, ``fields`` the groups (enumerable and unbounded) before the filters."""
+    variants_check_args(max_distinct, order, min_count, min_fill, show)
+    raws = [line.encode("utf-8", errors="surrogateescape") for line in split_lines(_as_text(logs))]
+    per_sig: Dict[int, int] = {}
+    groups: Dict[tuple, Dict[int, list]] = {}
+    tokens = field_lines = 0
+    for i, raw in enumerate(raws):
+        sig = line_signature(raw)
+        per_sig[sig] = per_sig.get(sig, 0) + 1
+        fields = line_fields(raw)
+        tokens += len(fields)
+        field_lines += bool(fields)
+        for j, _, tok in fields:
+            h = var_hash(tok)
+            v = groups.setdefault((sig, j), {}).setdefault(h, [0, i, i, h, raw])
+            v[0] += 1
+            v[2] = i
+    out = variants_head(len(raws), field_lines, tokens, len(per_sig), len(groups),
+                        sum(len(g) > max_distinct for g in groups.values()), max_distinct)
+    listed = []
+    for (sig, j), g in groups.items():
+        if len(g) > max_distinct:
+            continue
+        count = sum(v[0] for v in g.values())
+        if count < min_count or count < min_fill * per_sig[sig] or (varying and len(g) == 1):
+            continue
+        first = min(v[1] for v in g.values())
+        listed.append((variants_order_key(order, sig, j, count, count - max(v[0] for v in g.values()), len(g), first),
+                       sig, j, list(g.values())))
+    listed.sort(key=lambda g: g[0])
+    if top is not None:
+        listed = listed[:max(0, int(top))]
+    out["top"] = [variants_row(sig, j, per_sig[sig], [tuple(v) for v in vals], show) for _, sig, j, vals in listed]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Trends report (an extra, as the gap report): what changed over the time of this log? The log's
 # own earlier part is the baseline: lines are counted per *cell* (template signature, time bucket),
 # a *pivot* bucket splits the log's span, and a template started, stopped, surged, faded or stayed

@@ -910,7 +910,7 @@ I64_MAX = (1 << 63) - 1
 
 
 class _SlotTable:
-    """What the two device-resident hash tables share: the validation of ``cap`` / ``tile``, the
+    """What the device-resident hash tables share: the validation of ``cap`` / ``tile``, the
     slot counter, the capacity rule with its growth, and the rows. A subclass has its columns
     (``_alloc``, ``_tab``, ``_row_dtypes``), the names of its native calls and its ``fold``.
 
@@ -1335,6 +1335,133 @@ def line_values(text, line_start, line_len, cap: Optional[int] = None, per_block
         if m <= cap:
             return sig, out_line[:m], out_key[:m], out_val[:m], (m, lines)
         cap = m
+
+
+# ---------------------------------------------------------------------------------------------
+# variants report (csrc/kernels/variants.hip): template signature and token hashes of every line's
+# fields, the value table (var_table.h)
+
+VR_MAX_LINES = 2048         # lines per block of k_line_vars at most
+VT_TILE = 2048              # triples per block of k_var_fold at most
+VT_LDS_SLOTS = 1024         # slots of its LDS table: more distinct (field, value) in a tile go to HBM directly
+CT_MIX = 0x9E3779B97F4A7C15  # cell_key(field, value) = field + value * CT_MIX mod 2^64 (cell_table.h)
+I64_MIN = -(1 << 63)
+
+
+def line_vars(text, line_start, line_len, cap: Optional[int] = None, per_block: int = 0):
+    """Template signature and fields (``golden.line_fields``) of every line: (sig int64[L], line
+    int32[n], field int64[n], value int64[n], (n, lines with at least one field)) -- field j of
+    line i is the triple (i, ``golden.val_key(sig[i], j)``, ``golden.var_hash(token)``), whether
+    or not the token reads as a number. One pass over the text (k_line_vars) with the capacity
+    protocol of ``line_values``. ``per_block``: lines per block instead of the size the launch
+    picks (tests). GPU: the triples come in no particular order; CPU: in line order, the fields
+    of a line in byte order."""
+    dev = text.device
+    L = line_start.numel()
+    if per_block and not 0 < per_block <= VR_MAX_LINES:
+        raise ValueError("line_vars: per_block must be 1..%d" % VR_MAX_LINES)
+    sig = torch.empty(L, dtype=torch.int64, device=dev)
+    if L == 0:
+        return (sig, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev), (0, 0))
+    # a re-run costs a whole pass over the text, a triple 20 bytes: a log line holds a variable token or three
+    cap = max(1024, 3 * L) if cap is None else max(0, int(cap))
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_field = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        out_value = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        N.line_vars(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, sig.data_ptr(),
+                    out_line.data_ptr(), out_field.data_ptr(), out_value.data_ptr(), cap, cnt.data_ptr(), _s(text),
+                    text.is_cuda, per_block)
+        m, lines = cnt.tolist()
+        if m <= cap:
+            return sig, out_line[:m], out_field[:m], out_value[:m], (m, lines)
+        cap = m
+
+
+class VarTable(_SlotTable):
+    """Device-resident counts per (field, value): per pair its triples, its smallest and its
+    largest ordinal (global line numbers), kept across ``fold`` calls (the chunks of a stream).
+    The key column holds ``cell_key(field, value)``; two pairs that share it are one entry. GPU:
+    k_var_fold / k_var_rows / k_var_reinsert / k_var_winners; CPU: their host twins on the same
+    layout. Capacity and growth: ``_SlotTable``. ``tile``: triples per block of k_var_fold
+    (256..VT_TILE, a multiple of 256) instead of the size the launch picks (tests)."""
+
+    _max_tile = VT_TILE
+    _row_dtypes = (torch.int64,) * 5
+    _rows_op, _reinsert_op = "var_rows", "var_reinsert"
+
+    def _alloc(self, cap: int) -> None:
+        dev = self.device
+        self.cap = cap
+        self._key = torch.full((cap + 1,), GT_EMPTY, dtype=torch.int64, device=dev)
+        self._key[cap] = 0          # the side slot of the pair whose key equals the marker: unclaimed
+        self._field = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._value = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._first = torch.full((cap + 1,), I64_MAX, dtype=torch.int64, device=dev)
+        self._last = torch.full((cap + 1,), I64_MIN, dtype=torch.int64, device=dev)
+        self._used = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def _tab(self):
+        return (self._key.data_ptr(), self._field.data_ptr(), self._value.data_ptr(), self._count.data_ptr(),
+                self._first.data_ptr(), self._last.data_ptr(), self._used.data_ptr(), self.cap)
+
+    def rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(field, value, count, first, last) of every entry, int64 each, in no particular order."""
+        return self._rows(self.used)
+
+    def _triples(self, who: str, field, value, ord):
+        n = field.numel()
+        if value.numel() != n or ord.numel() != n:
+            raise ValueError("VarTable.%s: field, value and ord differ in length" % who)
+        return tuple(t.to(device=self.device, dtype=torch.int64).contiguous() for t in (field, value, ord))
+
+    def fold(self, field: torch.Tensor, value: torch.Tensor, ord: torch.Tensor, skip: Optional[GapTable] = None) -> None:
+        """Fold the triples (field[i], value[i], ord[i]) into the table; a triple whose field the
+        ``GapTable`` ``skip`` holds (as a signature) is dropped."""
+        field, value, ord = self._triples("fold", field, value, ord)
+        if skip is not None and skip.device != self.device:
+            raise ValueError("VarTable.fold: the skip set lives on %s, the table on %s" % (skip.device, self.device))
+        n = field.numel()
+        if n == 0:
+            return
+        self._reserve(n)
+        N.var_fold(self._tab(), None if skip is None else skip._tab(), field.data_ptr(), value.data_ptr(), ord.data_ptr(),
+                   n, _s(self._key), self._cuda, self.tile)
+
+    def winners(self, field: torch.Tensor, value: torch.Tensor, ord: torch.Tensor) -> torch.Tensor:
+        """The indices (int64, no particular order) of the triples whose entry exists and whose
+        ``first`` equals their ordinal: after a fold of the same triples, the lines that became a
+        value's first line."""
+        field, value, ord = self._triples("winners", field, value, ord)
+        n = field.numel()
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64, device=self.device)
+        out = torch.empty(n, dtype=torch.int64, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        N.var_winners(self._tab(), field.data_ptr(), value.data_ptr(), ord.data_ptr(), n, out.data_ptr(), cnt.data_ptr(),
+                      _s(self._key), self._cuda)
+        return out[:int(cnt.item())]
+
+    def purge(self, fields: torch.Tensor) -> int:
+        """Drop every entry whose field is in ``fields`` (int64): the rows, without those, into a
+        fresh table of the same capacity -- the path of growth. Returns the entries dropped."""
+        fields = fields.to(device=self.device, dtype=torch.int64)
+        used = self.used
+        if used == 0 or fields.numel() == 0:
+            return 0
+        rows = self._rows(used)
+        keep = ~torch.isin(rows[0], fields)
+        kept = int(keep.sum().item())
+        if kept == used:
+            return 0
+        rows = tuple(c[keep].contiguous() for c in rows)
+        self._alloc(self.cap)
+        self._reinsert(rows, kept)
+        self._bound = kept
+        return used - kept
 
 
 # ---------------------------------------------------------------------------------------------

@@ -414,7 +414,39 @@ def metric_log(n_lines: int, templates: List[str], seed: int = 0, burst_at: floa
     return "".join(line + "\n" for line in lines), burst
 
 
-TREND_T0_MS = 1758283200000         # 2025-09-19T12:00:00Z
+VARIANT_TEMPLATE = "2025-09-19T12:%02d:%02d.%03dZ INFO  [proxy] upstream returned status %d to worker %d for request %d"
+
+
+def variant_log(n_lines: int, templates: List[str], seed: int = 0, rare_from: float = 0.7, rare_to: float = 0.8,
+                crlf_rate: float = 0.0) -> Tuple[str, dict]:
+    """``metric_log``'s templated log with one extra template, ``INFO  [proxy] upstream returned
+    status %d to worker %d for request %d``, on about a tenth of its lines, and three planted
+    fields on it: field 0, the status, is ``200`` except on about a fifth of the template's lines
+    in [``rare_from * n_lines``, ``rare_to * n_lines``), where it is ``503``; field 1, the worker,
+    goes round ``0..7``; field 2 is a request id that never repeats. Returns (text, facts) with
+    ``facts``: ``template`` (the line behind its stamp, the fields still ``%d``), ``lines`` (the
+    template's lines), ``common`` / ``rare`` (the two status tokens), ``rareLines`` (the lines
+    that hold the rare one, 0-based and ascending), ``rareRange`` (the [lo, hi) they were confined
+    to), ``workers`` -- known by construction. ``crlf_rate``: the share of lines that end in
+    ``\\r\\n``."""
+    rng = random.Random(seed)
+    lines = templated_log(n_lines, templates, seed=seed).split("\n")[:n_lines]
+    lo, hi = int(rare_from * n_lines), int(rare_to * n_lines)
+    planted, rare = 0, []
+    for i in range(n_lines):
+        if rng.random() >= 0.1:
+            continue
+        odd = lo <= i < hi and rng.random() < 0.2
+        if odd:
+            rare.append(i)
+        lines[i] = VARIANT_TEMPLATE % ((i // 60) % 60, i % 60, i % 1000, 503 if odd else 200, planted % 8, 1000000 + i)
+        planted += 1
+    text = "".join(line + ("\r\n" if rng.random() < crlf_rate else "\n") for line in lines)
+    return text, {"template": VARIANT_TEMPLATE.split("Z ", 1)[1], "lines": planted, "common": "200", "rare": "503",
+                  "rareLines": rare, "rareRange": (lo, hi), "workers": 8}
+
+
+TREND_T0_MS = 1758283200000        # 2025-09-19T12:00:00Z
 TREND_STOPPED = "INFO  [lease] heartbeat: renewed leader lease, sequence %d"
 TREND_STARTED = "ERROR [net] connection reset by peer while reading from upstream %d"
 TREND_SURGED = "WARN  [gc] pause of %dms exceeded the budget"
