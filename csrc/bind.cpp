@@ -134,6 +134,57 @@ static VarRows vw_from(const py::tuple& t) {
   return R;
 }
 
+// (key, count, first, last, tmin, tmax, opens, closes, toklen, tok, used, cap) of a span table (span_table.h)
+static SpanTab spt_from(const py::tuple& t) {
+  SpanTab T;
+  T.key = P<int64_t>(t[0].cast<uint64_t>());
+  T.count = P<unsigned long long>(t[1].cast<uint64_t>());
+  T.first = P<long long>(t[2].cast<uint64_t>());
+  T.last = P<long long>(t[3].cast<uint64_t>());
+  T.tmin = P<long long>(t[4].cast<uint64_t>());
+  T.tmax = P<long long>(t[5].cast<uint64_t>());
+  T.opens = P<int64_t>(t[6].cast<uint64_t>());
+  T.closes = P<int64_t>(t[7].cast<uint64_t>());
+  T.toklen = P<int32_t>(t[8].cast<uint64_t>());
+  T.tok = P<uint64_t>(t[9].cast<uint64_t>());
+  T.used = P<unsigned long long>(t[10].cast<uint64_t>());
+  T.cap = t[11].cast<int64_t>();
+  return T;
+}
+
+// (key, count, first, last, tmin, tmax, opens, closes, toklen, tok) row columns
+static SpanRows spw_from(const py::tuple& t) {
+  SpanRows R;
+  R.key = P<int64_t>(t[0].cast<uint64_t>());
+  R.count = P<int64_t>(t[1].cast<uint64_t>());
+  R.first = P<int64_t>(t[2].cast<uint64_t>());
+  R.last = P<int64_t>(t[3].cast<uint64_t>());
+  R.tmin = P<int64_t>(t[4].cast<uint64_t>());
+  R.tmax = P<int64_t>(t[5].cast<uint64_t>());
+  R.opens = P<int64_t>(t[6].cast<uint64_t>());
+  R.closes = P<int64_t>(t[7].cast<uint64_t>());
+  R.toklen = P<int32_t>(t[8].cast<uint64_t>());
+  R.tok = P<uint64_t>(t[9].cast<uint64_t>());
+  return R;
+}
+
+// (line, key, tok, n, sig, eff, nl, text, tbytes, ls, line_base): the triples of a piece with its lines
+static SpanPairs spp_from(const py::tuple& t) {
+  SpanPairs X;
+  X.line = P<const int32_t>(t[0].cast<uint64_t>());
+  X.key = P<const int64_t>(t[1].cast<uint64_t>());
+  X.tok = P<const int32_t>(t[2].cast<uint64_t>());
+  X.n = t[3].cast<int64_t>();
+  X.sig = P<const int64_t>(t[4].cast<uint64_t>());
+  X.eff = P<const int64_t>(t[5].cast<uint64_t>());
+  X.nl = t[6].cast<int64_t>();
+  X.text = P<const uint8_t>(t[7].cast<uint64_t>());
+  X.tbytes = t[8].cast<int64_t>();
+  X.ls = P<const int64_t>(t[9].cast<uint64_t>());
+  X.line_base = t[10].cast<int64_t>();
+  return X;
+}
+
 // a GapTab used as a set, or None: the empty set
 static GapTab gt_from_opt(const py::object& o) {
   return o.is_none() ? GapTab{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0} : gt_from(o.cast<py::tuple>());
@@ -1367,6 +1418,69 @@ PYBIND11_MODULE(_lpnative, m) {
                      P<unsigned long long>(cnt)); },
         py::arg("tab"), py::arg("field"), py::arg("value"), py::arg("ord"), py::arg("n"), py::arg("out"), py::arg("cnt"),
         py::arg("stream"), py::arg("dev"));
+  // ---- spans report (spans.hip): stamp, signature and sampled keys of every line, the span table
+  m.def("span_keys", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, int min_len, int shift,
+                        uint64_t sig, uint64_t ts, uint64_t out_line, uint64_t out_key, uint64_t out_tok, int64_t cap,
+                        uint64_t cnt, uint64_t lvl, uint64_t s, bool dev, int per_block) {
+    SpanLinesArgs A;
+    A.text = P<const uint8_t>(text); A.tbytes = tbytes;
+    A.ls = P<const int64_t>(ls); A.ll = P<const int32_t>(ll); A.nl = nl;
+    A.min_len = min_len; A.shift = shift;
+    A.sig = P<int64_t>(sig); A.ts = P<int64_t>(ts);
+    A.out_line = P<int32_t>(out_line); A.out_key = P<int64_t>(out_key); A.out_tok = P<int32_t>(out_tok);
+    A.cap = cap;
+    A.cnt = P<unsigned long long>(cnt);
+    A.lvl = P<unsigned long long>(lvl);
+    if (dev) {
+      span_keys_dev(A, s, per_block);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    span_keys_host(A); },
+        py::arg("text"), py::arg("tbytes"), py::arg("ls"), py::arg("ll"), py::arg("nl"), py::arg("min_len"),
+        py::arg("shift"), py::arg("sig"), py::arg("ts"), py::arg("out_line"), py::arg("out_key"), py::arg("out_tok"),
+        py::arg("cap"), py::arg("cnt"), py::arg("lvl"), py::arg("stream"), py::arg("dev"), py::arg("per_block") = 0);
+  m.def("span_fold", [](py::tuple tab, py::tuple pairs, uint64_t s, bool dev) {
+    const SpanTab T = spt_from(tab);
+    const SpanPairs X = spp_from(pairs);
+    if (dev) {
+      span_fold_dev(T, X, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    span_fold_host(T, X); },
+        py::arg("tab"), py::arg("pairs"), py::arg("stream"), py::arg("dev"));
+  m.def("span_ends", [](py::tuple tab, py::tuple pairs, uint64_t s, bool dev) {
+    const SpanTab T = spt_from(tab);
+    const SpanPairs X = spp_from(pairs);
+    if (dev) {
+      span_ends_dev(T, X, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    span_ends_host(T, X); },
+        py::arg("tab"), py::arg("pairs"), py::arg("stream"), py::arg("dev"));
+  m.def("span_rows", [](py::tuple tab, py::tuple rows, int64_t out_cap, uint64_t cnt, uint64_t s, bool dev, int shift) {
+    const SpanTab T = spt_from(tab);
+    const SpanRows R = spw_from(rows);
+    if (dev) {
+      span_rows_dev(T, R, out_cap, P<unsigned long long>(cnt), s, shift);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    span_rows_host(T, R, out_cap, P<unsigned long long>(cnt), shift); },
+        py::arg("tab"), py::arg("rows"), py::arg("out_cap"), py::arg("cnt"), py::arg("stream"), py::arg("dev"),
+        py::arg("shift") = 0);
+  m.def("span_reinsert", [](py::tuple tab, py::tuple rows, int64_t n, uint64_t s, bool dev) {
+    const SpanTab T = spt_from(tab);
+    const SpanRows R = spw_from(rows);
+    if (dev) {
+      span_reinsert_dev(T, R, n, s);
+      return;
+    }
+    py::gil_scoped_release nogil;
+    span_reinsert_host(T, R, n); },
+        py::arg("tab"), py::arg("rows"), py::arg("n"), py::arg("stream"), py::arg("dev"));
   // ---- trends report (trends.hip): stamp and signature of every line, the cell table
   m.def("line_stamps", [](uint64_t text, int64_t tbytes, uint64_t ls, uint64_t ll, int64_t nl, uint64_t sig, uint64_t ts,
                           uint64_t s, bool dev, int per_block) {

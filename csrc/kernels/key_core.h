@@ -97,4 +97,45 @@ LP_HD void line_keys_at(const uint8_t* __restrict__ text, int64_t tbytes, int64_
   if (key_qualifies(S, min_len)) key_insert(K, (int64_t)S.h);
 }
 
+// ---- with the place of every token (spans.hip): the list beside KeyList. Slot j holds the token of
+// K.k[j] as (offset in the line) | (length << KEY_POS_LEN_SHIFT): the offset is below SIG_MAX_BYTES, the
+// length at most KEY_MAX_LEN. Indexed by unrolled constants only, as KeyList is.
+constexpr int KEY_POS_LEN_SHIFT = 10;
+constexpr int32_t KEY_POS_OFF_MASK = (1 << KEY_POS_LEN_SHIFT) - 1;
+
+struct KeyPosList {
+  int32_t p[KEY_PER_LINE] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+LP_HD int32_t key_pos_pack(int off, uint32_t len) { return (int32_t)off | (int32_t)(len << KEY_POS_LEN_SHIFT); }
+
+// key_insert that also notes where the token stands
+LP_HD void key_insert_at(KeyList& K, KeyPosList& P, int64_t key, int32_t pos) {
+  bool dup = false;
+#pragma unroll
+  for (int j = 0; j < KEY_PER_LINE; ++j) dup = dup || (j < K.n && K.k[j] == key);
+  const bool ins = !dup && K.n < KEY_PER_LINE;
+#pragma unroll
+  for (int j = 0; j < KEY_PER_LINE; ++j) {
+    const bool here = ins && j == K.n;
+    K.k[j] = here ? key : K.k[j];
+    P.p[j] = here ? pos : P.p[j];
+  }
+  K.n += ins ? 1 : 0;
+}
+
+// key_step for the byte at offset t of the line: a token that ends here stands at [t - len, t)
+LP_HD void key_step_at(KeyState& S, KeyList& K, KeyPosList& P, uint32_t c, int t, bool on, int min_len) {
+  const bool dg = c - '0' < 10u;
+  const bool al = dg || ((c | 32u) - 'a' < 26u);
+  if (on && !al && key_qualifies(S, min_len)) key_insert_at(K, P, (int64_t)S.h, key_pos_pack(t - (int)S.len, S.len));
+  if (on) {
+    const uint64_t v = sig_fold(S.len ? S.h : SIG_FNV_OFFSET, c | 32u);
+    S.h = al ? v : S.h;
+    S.dig = al ? ((S.len ? S.dig : 0u) | (dg ? 1u : 0u)) : 0u;
+    const uint32_t grown = S.len < (uint32_t)KEY_MAX_LEN + 1u ? S.len + 1u : S.len;
+    S.len = al ? grown : 0u;
+  }
+}
+
 }  // namespace lp

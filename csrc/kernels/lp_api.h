@@ -570,6 +570,63 @@ void var_winners_host(const VarTab& T, const int64_t* field, const int64_t* valu
                       int64_t* out, unsigned long long* cnt);
 }  // namespace lp
 
+// ---- spans report (spans.hip): stamp, signature and sampled keys of every line; a span per key
+#include "span_table.h"
+namespace lp {
+struct SpanLinesArgs {
+  const uint8_t* text;       // 16-byte aligned on the device
+  int64_t tbytes;            // bytes of `text` that may be read (lines are clipped to it)
+  const int64_t* ls; const int32_t* ll;
+  int64_t nl;                // lines of ls / ll, at most 2^31 - 1: every one is walked
+  int min_len;               // KEY_MIN_LEN_LO .. KEY_MAX_LEN
+  int shift;                 // 0..64: only the keys of this hash sample (span_sampled) are emitted
+  // outputs: sig[i] / ts[i] = template signature and stamp (TS_NONE: none) of line i, what
+  // line_stamps_dev writes; the sampled ones of every line's first 8 distinct keys (key_core.h) as
+  // (line number, key, place of the token: key_pos_pack) triples, the first `cap` of them;
+  // cnt[0] += triples (all of them: above cap the caller re-runs, as with line_keys_dev),
+  // cnt[1] += lines with at least one triple; lvl (optional): lvl[m] += the lines with a triple whose
+  // deepest key has level m (span_level) -- the lines that still hold a key under every shift <= m
+  int64_t* sig; int64_t* ts;
+  int32_t* out_line; int64_t* out_key; int32_t* out_tok;
+  int64_t cap;
+  unsigned long long* cnt;   // [2], zeroed by the caller
+  unsigned long long* lvl;   // [SPAN_LEVELS] or null
+};
+// per_block: lines per block (rounded up to a multiple of 256, at most 2048), 0: chosen from nl.
+// GPU: the triples come in no particular order
+void span_keys_dev(const SpanLinesArgs& A, uint64_t stream, int per_block = 0);
+// appends in line order, the keys of a line in byte order
+void span_keys_host(const SpanLinesArgs& A);
+struct SpanPairs {           // the triples of one span_keys call with what the table needs of its lines
+  const int32_t* line; const int64_t* key; const int32_t* tok;
+  int64_t n;
+  const int64_t* sig;        // [nl] signatures of the piece's lines
+  const int64_t* eff;        // [nl] effective times (TS_NONE: none)
+  int64_t nl;
+  const uint8_t* text; int64_t tbytes;   // the piece's text, still resident: the tokens are cut from it
+  const int64_t* ls;         // [nl] line starts in `text`
+  int64_t line_base;         // global number of the piece's line 0
+};
+// fold: count, first / last line and smallest / largest effective time per key. A pair whose line is
+// outside [0, nl) is counted in used[1]. The caller keeps 2 * (used + n) <= cap.
+void span_fold_dev(const SpanTab& T, const SpanPairs& X, uint64_t stream);
+// ends, after the fold of the SAME pairs on the same stream (first / last are final only then):
+// opens, toklen and tok from the pair that holds the span's first line, closes from the one that
+// holds its last
+void span_ends_dev(const SpanTab& T, const SpanPairs& X, uint64_t stream);
+// the occupied slots whose key is in sample `shift` (span_sampled; 0: all) as rows, in no particular
+// order: the first out_cap of them; *cnt += all of them
+void span_rows_dev(const SpanTab& T, const SpanRows& R, int64_t out_cap, unsigned long long* cnt, uint64_t stream,
+                   int shift = 0);
+// n rows of distinct keys into a table that holds none of them (growth, purge); used[0] is left to
+// the caller, who knows it is n
+void span_reinsert_dev(const SpanTab& T, const SpanRows& R, int64_t n, uint64_t stream);
+void span_fold_host(const SpanTab& T, const SpanPairs& X);
+void span_ends_host(const SpanTab& T, const SpanPairs& X);
+void span_rows_host(const SpanTab& T, const SpanRows& R, int64_t out_cap, unsigned long long* cnt, int shift = 0);
+void span_reinsert_host(const SpanTab& T, const SpanRows& R, int64_t n);
+}  // namespace lp
+
 // ---- log timeline (timeline.hip): the timestamp of every line, counts per time bucket
 namespace lp {
 // out[i] = epoch milliseconds (UTC) of the stamp at the head of line i, or TS_NONE = INT64_MIN

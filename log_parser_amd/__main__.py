@@ -48,6 +48,12 @@
                                                templates take: how often, where first and last, the
                                                field with one deviant among thousands first; several
                                                files continue ONE log (JSON)
+  spans     FILE... [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--min-length N]
+            [--min-lines N] [--max-share F] [--min-ms N] [--order duration|lines|first]
+            [--unfinished-only] [--max-ids N] [--top N] [--kinds N]
+                                               the lifetimes of the ids of a log: the longest first,
+                                               and the ones that never logged the line their kind
+                                               usually ends on; several files continue ONE log (JSON)
   trends    FILE [--patterns DIR] [--device D] [--stream] [--chunk-bytes N] [--bucket S]
             [--at T|first-event|first-error] [--ratio R] [--min-count N] [--kind K] [--order O]
             [--top N]
@@ -263,6 +269,27 @@ def cmd_variants(args, cfg: Config) -> int:
     return 0
 
 
+def cmd_spans(args, cfg: Config) -> int:
+    lp = _parser(args, cfg)
+    try:
+        acc = lp.span_accumulator(args.min_length, args.max_ids)
+        for path in args.files:             # several files continue ONE log
+            if args.stream:
+                from .api import _source
+                with _source(path) as src:
+                    acc.add_stream(src, args.chunk_bytes)
+            else:
+                with open(path, "rb") as f:
+                    acc.add_document(f.read())
+        rep = acc.report(top=args.top, order=args.order, unfinished_only=args.unfinished_only, min_lines=args.min_lines,
+                         max_share=args.max_share, min_ms=args.min_ms, kinds=args.kinds)
+    except ValueError as e:                 # a length, a count, a share or the limit of ids out of range
+        print(str(e), file=sys.stderr)
+        return 2
+    print(json.dumps(rep, ensure_ascii=False))
+    return 0
+
+
 def cmd_trends(args, cfg: Config) -> int:
     lp = _parser(args, cfg)
     at = int(args.at) if args.at is not None and args.at.lstrip("-").isdigit() else args.at
@@ -424,6 +451,27 @@ def main(argv: Optional[List[str]] = None) -> int:
     w.add_argument("--show", type=int, default=5, metavar="N",
                    help="values listed per field: all up to 2N, else the N most and the N least common (default 5)")
     w.add_argument("--top", type=int, default=20, help="fields reported (default 20)")
+    n = sub.add_parser("spans", help="the lifetimes of the ids of a log: the longest, and the ones that never ended")
+    n.add_argument("files", nargs="+", metavar="FILE")
+    _library_options(n)
+    n.add_argument("--stream", action="store_true", help="the files processed in chunks (same report)")
+    n.add_argument("--chunk-bytes", type=int, default=None, metavar="N", help="chunk size of --stream")
+    n.add_argument("--min-length", type=int, default=8, metavar="N",
+                   help="an id is a run of N..64 letters and digits that holds a digit (4..64, default 8)")
+    n.add_argument("--min-lines", type=int, default=2, metavar="N",
+                   help="list only the ids on at least N lines (default 2)")
+    n.add_argument("--max-share", type=float, default=0.25, metavar="F",
+                   help="drop the ids on more than this share of all lines: a host name is no id (default 0.25)")
+    n.add_argument("--min-ms", type=int, default=0, metavar="N",
+                   help="list only the spans that lasted at least N milliseconds (default 0)")
+    n.add_argument("--order", choices=("duration", "lines", "first"), default="duration",
+                   help="longest span first (default), most lines first, or in order of first appearance")
+    n.add_argument("--unfinished-only", action="store_true",
+                   help="list only the spans that did not close on the template their kind usually ends on")
+    n.add_argument("--max-ids", type=int, default=1 << 22, metavar="N",
+                   help="ids kept at most; above that the report is one of a hash sample (16..2^26, default 2^22)")
+    n.add_argument("--top", type=int, default=20, help="spans reported (default 20)")
+    n.add_argument("--kinds", type=int, default=10, help="kinds of span reported (default 10)")
     d = sub.add_parser("trends", help="line templates of a log file that started, stopped, surged or faded over its time")
     d.add_argument("file")
     _library_options(d)
@@ -484,7 +532,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     return {"analyze": cmd_analyze, "validate": cmd_validate, "gaps": cmd_gaps,
             "timeline": cmd_timeline, "novel": cmd_novel, "traces": cmd_traces,
             "leadup": cmd_leadup, "correlate": cmd_correlate, "values": cmd_values,
-            "variants": cmd_variants,
+            "variants": cmd_variants, "spans": cmd_spans,
             "trends": cmd_trends, "pauses": cmd_pauses, "cadence": cmd_cadence}[args.cmd](args, cfg)
 
 

@@ -42,6 +42,7 @@ SOURCES = [
     ("kernels/correlate.hip", "hip"),
     ("kernels/values.hip", "hip"),
     ("kernels/variants.hip", "hip"),
+    ("kernels/spans.hip", "hip"),
     ("kernels/timeline.hip", "hip"),
     ("kernels/trends.hip", "hip"),
     ("kernels/pauses.hip", "hip"),

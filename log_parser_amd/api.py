@@ -57,6 +57,11 @@ to embedders, with what an in-process user needs beyond one call at a time:
   beats they missed and the ones that stopped before the log ended -- ``golden.cadence``;
   ``cadence_stream`` / ``cadence_resident`` for one log too large for one piece,
   ``cadence_accumulator`` for a log that arrives over time;
+* ``spans`` / ``spans_file``: the lifetimes of the ids of a log -- per id its lines, first and last
+  line, duration and the templates it opens and closes on; the longest first, and the ones that
+  never logged the line their kind usually ends on -- ``golden.spans``; ``spans_stream`` /
+  ``spans_resident`` for one log too large for one piece, ``span_accumulator`` for a log that
+  arrives over time;
 * the frequency-tracking surface: ``pattern_frequency``, ``frequency_statistics``,
   ``reset_pattern_frequency``, ``reset_all_frequencies``.
 """
@@ -544,6 +549,70 @@ class LogParser:
                           min_count: int = 5, min_fill: float = 0.9, varying: bool = True, show: int = 5) -> dict:
         """``variants`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
         return self.variants_stream(resident, None, max_distinct, top, order, min_count, min_fill, varying, show)
+
+    # ---- spans report ------------------------------------------------------------------------
+    def spans(self, logs, min_len: int = 8, max_ids: int = 1 << 22, top: Optional[int] = 20, order: str = "duration",
+              unfinished_only: bool = False, min_lines: int = 2, max_share: float = 0.25, min_ms: int = 0,
+              kind_min_spans: int = 5, close_share=0.8, kinds: Optional[int] = 10) -> dict:
+        """The lifetimes of the ids of one document (str or bytes): which request, job, trace or
+        connection took longest, and which started like all the others and never logged the line
+        the others end on? An id is a key token of ``correlate`` (``min_len``..64 letters and
+        digits with a digit, case folded; the first 8 of a line); its *span* is every line that
+        holds it: ``lines``, ``firstLine`` / ``lastLine``, ``start`` / ``end`` (the smallest and
+        largest time of its lines, a line's time being the stamp of the nearest stamped line at or
+        before it), ``durationMs``, and ``opens`` / ``closes``, the templates of its first and last
+        line. Listed are the spans with ``lines >= min_lines``, ``lines <= max_share *
+        totalLines`` (a host name on every line is no id) and ``durationMs >= min_ms``. Spans
+        that open alike are a *kind*; a kind of at least ``kind_min_spans`` spans of which a
+        share of ``close_share`` close on one template has that template as its *usual end*, and a
+        span of the kind that closes otherwise is *unfinished*. ``kinds``: the kinds, those with
+        unfinished spans first; ``top``: the spans (``unfinished_only``: only those) by
+        ``order="duration"``, ``"lines"`` or ``"first"``. At most ``max_ids`` (16..2^26) ids are
+        kept: above that the report is one of a hash sample of the ids (``sampleShift``). No
+        pattern takes part. ``Engine.spans_bytes``; ``golden.spans`` is the specification; the
+        frequency window is not touched."""
+        from .spans import check_args
+        check_args(min_len, max_ids, order, min_lines, max_share, min_ms, kind_min_spans, close_share, top, kinds)
+        if isinstance(logs, str):
+            logs = logs.encode("utf-8", errors="surrogateescape")
+        with self._engine_guard("spans"):
+            return self.engine.spans_bytes(logs, min_len=min_len, max_ids=max_ids, top=top, order=order,
+                                           unfinished_only=unfinished_only, min_lines=min_lines, max_share=max_share,
+                                           min_ms=min_ms, kind_min_spans=kind_min_spans, close_share=close_share,
+                                           kinds=kinds)
+
+    def spans_file(self, path: str, min_len: int = 8, max_ids: int = 1 << 22, **report) -> dict:
+        """``spans`` of a log file, read as ONE document whatever its size (``report``: the other
+        parameters of ``spans``)."""
+        from .spans import check_args
+        check_args(min_len, max_ids, **{k: v for k, v in report.items() if k != "unfinished_only"})
+        with open(path, "rb") as f:
+            return self.spans(f.read(), min_len, max_ids, **report)
+
+    def span_accumulator(self, min_len: int = 8, max_ids: int = 1 << 22):
+        """A ``spans.SpanAccumulator`` on this parser's engine for a log that arrives over time
+        (``add_document`` / ``add_stream`` / ``add_resident`` continue ONE log, then ``report``);
+        each of its calls runs under the batcher guard and the lock of ``spans``. ``min_len`` and
+        ``max_ids`` are fixed here."""
+        from .spans import SpanAccumulator
+        with self._engine_guard("spans"):
+            return SpanAccumulator(self.engine, min_len, max_ids, guard=lambda: self._engine_guard("spans"))
+
+    def spans_stream(self, src_or_path, chunk_bytes: Optional[int] = None, min_len: int = 8, max_ids: int = 1 << 22,
+                     **report) -> dict:
+        """``spans`` of ONE large log processed in line-aligned chunks (the chunks of
+        ``gaps_stream``): a bytes-like source, or the path of a file (mmap'd). Exactly the
+        one-document report, whatever the chunk size (spans.py says why)."""
+        from .spans import check_args
+        check_args(min_len, max_ids, **{k: v for k, v in report.items() if k != "unfinished_only"})
+        acc = self.span_accumulator(min_len, max_ids)
+        with _source(src_or_path) as src:
+            acc.add_stream(src, chunk_bytes)
+        return acc.report(**report)
+
+    def spans_resident(self, resident, min_len: int = 8, max_ids: int = 1 << 22, **report) -> dict:
+        """``spans`` of a log held in HBM (``load_resident``), read in place chunk by chunk."""
+        return self.spans_stream(resident, None, min_len, max_ids, **report)
 
     # ---- trends report -----------------------------------------------------------------------
     def trends(self, logs, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,

@@ -912,6 +912,18 @@ class Engine:
         from .variants import variants_document
         return variants_document(self, bytes(data), max_distinct, top, order, min_count, min_fill, varying, show)
 
+    # ------------------------------------------------------------------ spans report
+    def spans_bytes(self, data: bytes, min_len: int = 8, max_ids: int = 1 << 22, top: Optional[int] = 20,
+                    order: str = "duration", unfinished_only: bool = False, min_lines: int = 2, max_share: float = 0.25,
+                    min_ms: int = 0, kind_min_spans: int = 5, close_share=0.8, kinds: Optional[int] = 10) -> dict:
+        """The lifetimes of the ids of one document: which took longest, and which never logged the
+        line the others end on? (spans.py; ``golden.spans`` is the specification.) The matchers do
+        not run, nothing is scored and the frequency window is not touched."""
+        from .spans import spans_document
+        return spans_document(self, bytes(data), min_len, max_ids, top=top, order=order, unfinished_only=unfinished_only,
+                              min_lines=min_lines, max_share=max_share, min_ms=min_ms, kind_min_spans=kind_min_spans,
+                              close_share=close_share, kinds=kinds)
+
     # ------------------------------------------------------------------ trends report
     def trends_bytes(self, data: bytes, bucket_seconds: int = 60, at=None, ratio: int = 4, min_count: int = 5,
                      kind: Optional[str] = None, order: str = "change", top: Optional[int] = 20,

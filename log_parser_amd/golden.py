@@ -1607,6 +1607,244 @@ def cadence(logs, min_ms: int = 1000, ratio: int = 4, min_count: int = 5, min_re
 
 
 # ---------------------------------------------------------------------------------------------
+# Spans report (an extra, as the gap report): which request, job, trace or connection took longest,
+# and which started like all the others and never logged the line the others end on? The *span* of
+# an id is the set of lines that hold it; a hung request is invisible to ``pauses`` and ``cadence``
+# -- the other requests keep the log and the templates busy -- and to ``correlate`` when no pattern
+# matches. No pattern takes part here. These functions are the specification of
+# ``log_parser_amd/spans.py`` and of the span kernels (csrc/kernels/spans.hip, span_table.h).
+#
+# Known limits: those of ``line_keys`` (two tokens may share a 64-bit key; a UUID is two tokens;
+# the first ``KEY_PER_LINE`` distinct keys of a line's first ``SIG_MAX_BYTES`` bytes); stamps lie
+# within +-2^61 ms, as for ``pauses``, so no duration overflows 64 bits; under sampling
+# (``sampleShift > 0``) every count is a count of the sample.
+
+SPAN_ORDERS = ("duration", "lines", "first")
+SPAN_MAX_IDS_LO, SPAN_MAX_IDS_HI, SPAN_MAX_IDS = 16, 1 << 26, 1 << 22
+SPAN_BUCKETS = 64
+
+
+def _span_int(name: str, v, lo: int, hi: Optional[int] = None) -> None:
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        raise ValueError("spans: %s must be an integer %s" % (name, (">= %d" % lo) if hi is None else "in %d..%d" % (lo, hi)))
+
+
+def spans_check_args(min_len: int = 8, max_ids: int = SPAN_MAX_IDS, order: str = "duration", min_lines: int = 2,
+                     max_share: float = 0.25, min_ms: int = 0, kind_min_spans: int = 5, close_share=0.8,
+                     top: Optional[int] = 20, kinds: Optional[int] = 10) -> Fraction:
+    """``close_share`` as an exact fraction, or ValueError. A float stands for the decimal it prints
+    as -- 0.8 is 4/5, not the binary fraction next to it -- so a share of exactly ``close_share``
+    passes."""
+    _span_int("min_len", min_len, KEY_MIN_LEN, KEY_MAX_LEN)
+    _span_int("max_ids", max_ids, SPAN_MAX_IDS_LO, SPAN_MAX_IDS_HI)
+    if order not in SPAN_ORDERS:
+        raise ValueError("spans: order must be 'duration', 'lines' or 'first'")
+    _span_int("min_lines", min_lines, 1)
+    if isinstance(max_share, bool) or not isinstance(max_share, (int, float)) or not 0.0 < max_share <= 1.0:
+        raise ValueError("spans: max_share must be in (0, 1]")
+    _span_int("min_ms", min_ms, 0)
+    _span_int("kind_min_spans", kind_min_spans, 1)
+    if isinstance(close_share, bool) or not isinstance(close_share, (int, float, Fraction)) \
+            or close_share != close_share or not 0 < close_share <= 1:
+        raise ValueError("spans: close_share must be a number in (0, 1]")
+    for name, v in (("top", top), ("kinds", kinds)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise ValueError("spans: %s must be None or an integer" % name)
+    return Fraction(repr(close_share)) if isinstance(close_share, float) else Fraction(close_share)
+
+
+def span_level(key: int) -> int:
+    """The deepest sample that holds ``key``: the leading zero bits of ``fmix64(key)`` (0..64). A key
+    is in sample s -- the top s bits of the hash are zero -- exactly when ``span_level(key) >= s``:
+    the samples are nested."""
+    return 64 - fmix64(key).bit_length()
+
+
+def spans_shift(levels: Sequence[int], max_ids: int) -> int:
+    """The smallest s whose sample holds at most ``max_ids`` of the ids with these levels."""
+    s = 0
+    while sum(1 for v in levels if v >= s) > max_ids:
+        s += 1
+    return s
+
+
+def spans_head(total: int, timed: int, id_lines: int, pairs: int, ids: int, min_len: int, max_ids: int,
+               shift: int) -> dict:
+    """The head of the report; nothing listed yet."""
+    return {"totalLines": total, "timedLines": timed, "idLines": id_lines, "pairs": pairs, "ids": ids, "listed": 0,
+            "minLength": min_len, "maxIds": max_ids, "sampleShift": shift, "durations": [], "kinds": [], "top": []}
+
+
+def spans_durations(hist: Sequence[int]) -> list:
+    """The duration histogram (``hist[b]``: listed timed spans whose duration has bit length b)."""
+    return [{"fromMs": (1 << b) >> 1, "toMs": 1 << b, "count": c} for b, c in enumerate(hist) if c]
+
+
+def spans_usual_end(closes: Dict[int, int], spans_n: int, kind_min_spans: int, close_share: Fraction) -> Optional[int]:
+    """The usual end of a kind with ``spans_n`` spans whose closing templates (unsigned signature
+    -> spans) are ``closes``: the one with the most spans, the smaller signature on a tie -- if
+    the kind has at least ``kind_min_spans`` spans and that one's share reaches ``close_share``."""
+    if spans_n < kind_min_spans:
+        return None
+    sig, c = min(closes.items(), key=lambda kv: (-kv[1], kv[0]))
+    return sig if Fraction(c, spans_n) >= close_share else None
+
+
+def spans_order_key(order: str, duration: Optional[int], lines: int, first: int, key: int):
+    if order == "duration":
+        return (duration is None, -(duration or 0), first, key)
+    if order == "lines":
+        return (-lines, first, key)
+    return (first, key)
+
+
+def _span_text(raw: bytes) -> str:
+    return raw.decode("utf-8", errors="replace")
+
+
+def spans_kind_row(opens: int, spans_n: int, timed: int, sum_ms: int, max_ms: Optional[int], max_key: Optional[str],
+                   max_line: Optional[int], first_line: int, closes: Dict[int, int], usual: Optional[int],
+                   unfinished: int, raws: Dict[int, bytes]) -> dict:
+    """One row of ``kinds`` (lines 0-based; ``raws``: unsigned signature -> the first line of the
+    log with that template, for ``opens`` and every closing template): ValueError unless every such
+    line has its template."""
+    for s in [opens] + list(closes):
+        if line_signature(raws[s]) != s:
+            raise ValueError("spans: the example of %016x does not have that template" % s)
+    return {"opens": "%016x" % opens, "template": _span_text(line_template(raws[opens])),
+            "example": _span_text(raws[opens]), "firstLine": first_line + 1, "spans": spans_n, "timedSpans": timed,
+            "sumMs": sum_ms, "maxMs": max_ms, "maxKey": max_key, "maxLine": None if max_line is None else max_line + 1,
+            "closes": [{"signature": "%016x" % s, "spans": c, "template": _span_text(line_template(raws[s]))}
+                       for s, c in sorted(closes.items(), key=lambda kv: (-kv[1], kv[0]))],
+            "usualEnd": None if usual is None else "%016x" % usual, "unfinished": unfinished}
+
+
+def spans_row(key: int, token: bytes, lines: int, first: int, last: int, tmin: Optional[int], tmax: Optional[int],
+              opens: int, closes: int, unfinished: bool, usual: Optional[int], raw_open: bytes, raw_close: bytes) -> dict:
+    """One row of ``top`` from its numbers (lines 0-based; ``tmin`` None: no line of the span has a
+    time) and the example lines of its two templates: ValueError unless the token hashes to the
+    key, the numbers are those of a span and the examples have their templates."""
+    if fnv1a64(token) != key or token != token.lower():
+        raise ValueError("spans: the token %r does not hash to the key %016x" % (token, key))
+    if not (0 <= first <= last and 0 < lines <= last - first + 1) or (tmin is not None and tmin > tmax):
+        raise ValueError("spans: %016x has %d lines in %d..%d, or ends before it starts" % (key, lines, first + 1, last + 1))
+    if line_signature(raw_open) != opens or line_signature(raw_close) != closes:
+        raise ValueError("spans: an example of %016x does not have its template" % key)
+    row = {"key": token.decode("ascii"), "signature": "%016x" % key, "lines": lines, "firstLine": first + 1,
+           "lastLine": last + 1, "start": None if tmin is None else iso_ms(tmin),
+           "end": None if tmin is None else iso_ms(tmax), "durationMs": None if tmin is None else tmax - tmin,
+           "opens": "%016x" % opens, "closes": "%016x" % closes, "opensExample": _span_text(raw_open),
+           "closesExample": _span_text(raw_close), "unfinished": unfinished}
+    if usual is not None:
+        row["usualEnd"] = "%016x" % usual
+    return row
+
+
+def spans(logs, min_len: int = 8, max_ids: int = SPAN_MAX_IDS, top: Optional[int] = 20, order: str = "duration",
+          unfinished_only: bool = False, min_lines: int = 2, max_share: float = 0.25, min_ms: int = 0,
+          kind_min_spans: int = 5, close_share=0.8, kinds: Optional[int] = 10) -> dict:
+    """The spans report of ``logs`` (str or bytes). The keys of a line are ``line_keys(line,
+    min_len)``; its *time* is the stamp (``line_timestamp``) of the nearest stamped line at or
+    before it, none in front of the first stamp. The *span* of a key is every line that holds it:
+    ``lines``, ``firstLine`` / ``lastLine``, ``start`` / ``end`` (the smallest and the largest time
+    of its timed lines -- min and max, not the times of its first and last line),
+    ``durationMs = end - start`` (None when no line of it has a time), ``opens`` / ``closes`` (the
+    template signatures of its first and last line) and ``key``, the lowered token of its first line.
+
+    Sampling bounds the ids: with ``s = sampleShift`` the smallest number for which at most
+    ``max_ids`` ids have ``span_level(key) >= s``, only those ids exist for the report -- ``ids``,
+    ``pairs`` (their lines, summed) and ``idLines`` (the lines that hold at least one) count them.
+
+    Filters, in this order: ``lines >= min_lines``; ``lines <= max_share * totalLines``;
+    ``durationMs >= min_ms`` (None passes only for ``min_ms == 0``). ``listed`` counts the
+    survivors, ``durations`` their durations by ``pause_bucket``. They are grouped into *kinds* by
+    ``opens``: ``spans``, ``timedSpans``, ``sumMs``, ``maxMs`` with ``maxKey`` / ``maxLine`` (the
+    span's first line; the smallest (first line, key) on a tie), ``firstLine`` (the smallest first
+    line of its spans), ``closes`` (closing templates with their spans) and ``usualEnd``
+    (``spans_usual_end``). A span is *unfinished* when its kind has a usual end and its own
+    ``closes`` differs. ``kinds``: by (-unfinished, -spans, first line, signature), ``kinds`` of
+    them. ``top``: the spans, or with ``unfinished_only`` the unfinished ones, in ``order``
+    (``spans_order_key``), ``top`` of them; each names the example lines -- the first line of the
+    log with that template -- of its ``opens`` and ``closes``."""
+    share = spans_check_args(min_len, max_ids, order, min_lines, max_share, min_ms, kind_min_spans, close_share, top, kinds)
+    raws = [line.encode("utf-8", errors="surrogateescape") for line in split_lines(_as_text(logs))]
+    sigs = [line_signature(raw) for raw in raws]
+    first_of: Dict[int, int] = {}
+    for i, s in enumerate(sigs):
+        first_of.setdefault(s, i)
+    eff, now = [], None
+    for raw in raws:
+        t = line_timestamp(raw)
+        now = now if t is None else t
+        eff.append(now)
+    per_line = [line_key_tokens(raw, min_len) for raw in raws]
+    level = {k: span_level(k) for toks in per_line for k, _ in toks}
+    shift = spans_shift(list(level.values()), max_ids)
+    found: Dict[int, list] = {}         # key -> [lines, first, last, tmin, tmax, token]
+    id_lines = pairs = 0
+    for i, toks in enumerate(per_line):
+        held = [(k, t) for k, t in toks if level[k] >= shift]
+        id_lines += bool(held)
+        pairs += len(held)
+        for k, t in held:
+            g = found.setdefault(k, [0, i, i, None, None, t])
+            g[0] += 1
+            g[2] = i
+            if eff[i] is not None:
+                g[3] = eff[i] if g[3] is None else min(g[3], eff[i])
+                g[4] = eff[i] if g[4] is None else max(g[4], eff[i])
+    out = spans_head(len(raws), sum(t is not None for t in eff), id_lines, pairs, len(found), min_len, max_ids, shift)
+    dur = lambda g: None if g[3] is None else g[4] - g[3]
+    listed = {k: g for k, g in found.items()
+              if g[0] >= min_lines and g[0] <= max_share * len(raws)
+              and ((dur(g) is None and min_ms == 0) or (dur(g) is not None and dur(g) >= min_ms))}
+    out["listed"] = len(listed)
+    hist = [0] * SPAN_BUCKETS
+    by_kind: Dict[int, list] = {}
+    for k, g in listed.items():
+        if dur(g) is not None:
+            hist[pause_bucket(dur(g))] += 1
+        by_kind.setdefault(sigs[g[1]], []).append(k)
+    out["durations"] = spans_durations(hist)
+    usual: Dict[int, Optional[int]] = {}
+    kind_rows = []
+    for o, keys in by_kind.items():
+        closes: Dict[int, int] = {}
+        for k in keys:
+            c = sigs[listed[k][2]]
+            closes[c] = closes.get(c, 0) + 1
+        usual[o] = u = spans_usual_end(closes, len(keys), kind_min_spans, share)
+        unfinished = 0 if u is None else sum(1 for k in keys if sigs[listed[k][2]] != u)
+        timed = [k for k in keys if dur(listed[k]) is not None]
+        best = min(timed, key=lambda k: (-dur(listed[k]), listed[k][1], k)) if timed else None
+        first_line = min(listed[k][1] for k in keys)
+        kind_rows.append(((-unfinished, -len(keys), first_line, o),
+                          (o, len(keys), len(timed), sum(dur(listed[k]) for k in timed),
+                           None if best is None else dur(listed[best]),
+                           None if best is None else listed[best][5].decode("ascii"),
+                           None if best is None else listed[best][1], first_line, closes, u, unfinished,
+                           {s: raws[first_of[s]] for s in [o] + list(closes)})))
+    kind_rows.sort(key=lambda kv: kv[0])
+    if kinds is not None:
+        kind_rows = kind_rows[:max(0, kinds)]
+    out["kinds"] = [spans_kind_row(*row) for _, row in kind_rows]
+
+    def is_unfinished(k):
+        u = usual[sigs[listed[k][1]]]
+        return u is not None and sigs[listed[k][2]] != u
+
+    rows = [k for k in listed if not unfinished_only or is_unfinished(k)]
+    rows.sort(key=lambda k: spans_order_key(order, dur(listed[k]), listed[k][0], listed[k][1], k))
+    if top is not None:
+        rows = rows[:max(0, top)]
+    for k in rows:
+        n, first, last, tmin, tmax, tok = listed[k]
+        out["top"].append(spans_row(k, tok, n, first, last, tmin, tmax, sigs[first], sigs[last], is_unfinished(k),
+                                    usual[sigs[first]], raws[first_of[sigs[first]]], raws[first_of[sigs[last]]]))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Trace report (an extra, as the gap report): which stack traces does a log hold, how often, where
 # first, with which root cause, and does any pattern explain them? These functions are the
 # specification of ``log_parser_amd/traces.py`` and of the line classifier and the run scan

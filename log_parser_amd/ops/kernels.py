@@ -1465,9 +1465,172 @@ class VarTable(_SlotTable):
 
 
 # ---------------------------------------------------------------------------------------------
+# spans report (csrc/kernels/spans.hip): stamp, signature and sampled keys of every line from one
+# visit, the span table (span_table.h)
+
+SK_MAX_LINES = 2048         # lines per block of k_span_keys at most
+SPAN_TOK_BYTES = 64         # bytes of a span's token column (KEY_MAX_LEN)
+SPAN_LEVELS = 65            # levels of a key: the leading zero bits of its hash, 0..64
+KEY_POS_LEN_SHIFT = 10      # a token's place: offset in the line | length << 10 (csrc/kernels/key_core.h)
+
+
+def span_keys(text, line_start, line_len, min_len: int = 8, shift: int = 0, cap: Optional[int] = None,
+              per_block: int = 0, levels: Optional[torch.Tensor] = None):
+    """Stamp, template signature and keys of every line from ONE visit: (sig int64[L], ts int64[L],
+    line int32[n], key int64[n], tok int32[n], (n, lines with at least one triple)). ``sig`` / ``ts``
+    are those of ``line_stamps``; the triples are the keys of ``line_keys`` (every line, no table)
+    that lie in the hash sample ``shift`` -- the top ``shift`` bits of ``golden.fmix64(key)`` are
+    zero -- each with the place of its token, ``offset in the line | length << 10``. ``levels``
+    (int64[65] on the text's device, optional): ``levels[m]`` grows by the lines with a triple whose
+    deepest key has ``golden.span_level`` m. One pass over the text (k_span_keys) with the capacity
+    protocol of ``line_keys``. ``per_block``: lines per block instead of the size the launch picks
+    (tests). GPU: the triples come in no particular order; CPU: in line order, the keys of a line
+    in byte order."""
+    dev = text.device
+    L = line_start.numel()
+    if line_start.dtype != torch.int64 or not line_start.is_contiguous():
+        raise ValueError("span_keys: line_start must be contiguous int64[L]")
+    if line_len.dtype != torch.int32 or line_len.numel() != L or not line_len.is_contiguous():
+        raise ValueError("span_keys: line_len must be contiguous int32[L]")
+    if text.dtype != torch.uint8 or not text.is_contiguous() or line_start.device != dev or line_len.device != dev:
+        raise ValueError("span_keys: text must be contiguous uint8, the line index on its device")
+    if not KEY_MIN_LEN <= min_len <= KEY_MAX_LEN:
+        raise ValueError("span_keys: min_len must be %d..%d" % (KEY_MIN_LEN, KEY_MAX_LEN))
+    if not 0 <= shift <= 64:
+        raise ValueError("span_keys: shift must be 0..64")
+    if per_block and not 0 < per_block <= SK_MAX_LINES:
+        raise ValueError("span_keys: per_block must be 1..%d" % SK_MAX_LINES)
+    if levels is not None and (levels.dtype != torch.int64 or levels.numel() != SPAN_LEVELS or levels.device != dev
+                               or not levels.is_contiguous()):
+        raise ValueError("span_keys: levels must be contiguous int64[%d] on the text's device" % SPAN_LEVELS)
+    sig = torch.empty(L, dtype=torch.int64, device=dev)
+    ts = torch.empty(L, dtype=torch.int64, device=dev)
+    if L == 0:
+        return (sig, ts, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev), (0, 0))
+    # a re-run costs a whole pass over the text, a triple 16 bytes: a line of a service log holds an id or two
+    cap = max(1024, 2 * L) if cap is None else max(0, int(cap))
+    while True:
+        out_line = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        out_key = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        out_tok = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        lvl = None if levels is None else torch.zeros(SPAN_LEVELS, dtype=torch.int64, device=dev)
+        N.span_keys(text.data_ptr(), text.numel(), line_start.data_ptr(), line_len.data_ptr(), L, int(min_len), int(shift),
+                    sig.data_ptr(), ts.data_ptr(), out_line.data_ptr(), out_key.data_ptr(), out_tok.data_ptr(), cap,
+                    cnt.data_ptr(), _p(lvl), _s(text), text.is_cuda, per_block)
+        m, lines = cnt.tolist()
+        if m <= cap:
+            if levels is not None:
+                levels += lvl               # (only the run that fits counts)
+            return sig, ts, out_line[:m], out_key[:m], out_tok[:m], (m, lines)
+        cap = m
+
+
+class SpanTable(_SlotTable):
+    """Device-resident spans per key: per id its pairs (lines), its smallest and largest global
+    line number, the smallest and largest effective time of its timed lines, the template
+    signatures of its first and last line and the lowered token of its first line, kept across
+    ``fold`` calls (the chunks of a stream). GPU: k_span_fold / k_span_ends / k_span_rows /
+    k_span_reinsert; CPU: their host twins on the same layout. Capacity and growth: ``_SlotTable``."""
+
+    _max_tile = 2048
+    _rows_op, _reinsert_op = "span_rows", "span_reinsert"
+
+    def _alloc(self, cap: int) -> None:
+        dev = self.device
+        self.cap = cap
+        self._key = torch.full((cap + 1,), GT_EMPTY, dtype=torch.int64, device=dev)
+        self._key[cap] = 0          # the side slot of the key that equals the marker: unclaimed
+        self._count = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._first = torch.full((cap + 1,), I64_MAX, dtype=torch.int64, device=dev)
+        self._last = torch.full((cap + 1,), I64_MIN, dtype=torch.int64, device=dev)
+        self._tmin = torch.full((cap + 1,), I64_MAX, dtype=torch.int64, device=dev)
+        self._tmax = torch.full((cap + 1,), I64_MIN, dtype=torch.int64, device=dev)
+        self._opens = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._closes = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        self._toklen = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
+        self._tok = torch.zeros((cap + 1, SPAN_TOK_BYTES), dtype=torch.uint8, device=dev)
+        self._used = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def _tab(self):
+        return (self._key.data_ptr(), self._count.data_ptr(), self._first.data_ptr(), self._last.data_ptr(),
+                self._tmin.data_ptr(), self._tmax.data_ptr(), self._opens.data_ptr(), self._closes.data_ptr(),
+                self._toklen.data_ptr(), self._tok.data_ptr(), self._used.data_ptr(), self.cap)
+
+    def _rows(self, n: int, shift: int = 0):
+        """Every column of the occupied slots whose key is in sample ``shift``, in no particular
+        order: ``n`` is their number where the caller knows it (``shift == 0``: the occupied
+        slots), else an upper bound, and the rows are cut to the number found."""
+        dev = self.device
+        cols = tuple(torch.empty(n, dtype=torch.int64, device=dev) for _ in range(8)) \
+            + (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, SPAN_TOK_BYTES), dtype=torch.uint8, device=dev))
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        N.span_rows(self._tab(), tuple(c.data_ptr() for c in cols), n, cnt.data_ptr(), _s(self._key), self._cuda, int(shift))
+        found = int(cnt.item())
+        if found > n or (shift == 0 and found != n):
+            raise RuntimeError("SpanTable: %d occupied slots, the counter says %d" % (found, n))
+        return cols if found == n else tuple(c[:found].contiguous() for c in cols)
+
+    def rows(self):
+        """(key, count, first, last, tmin, tmax, opens, closes: int64[n]; toklen int32[n]; tok
+        uint8[n, 64]) of every span, in no particular order. ``tmin > tmax``: no line of the span
+        has a time."""
+        return self._rows(self.used)
+
+    def fold(self, line: torch.Tensor, key: torch.Tensor, tok: torch.Tensor, sig: torch.Tensor, eff: torch.Tensor,
+             text: torch.Tensor, line_start: torch.Tensor, line_base: int) -> None:
+        """Fold the triples of ONE ``span_keys`` call -- (line[i], key[i], tok[i]), lines counted
+        within the piece -- into the table: fold, then ends. ``sig`` / ``eff`` (int64[L]): the
+        signatures and effective times (``TS_NONE``: none) of the piece's lines; ``text`` /
+        ``line_start``: the piece itself, from which the tokens are cut; ``line_base``: the global
+        number of its line 0. A key whose first line lies in this call gets ``opens`` and its token
+        here; ``closes`` is rewritten by every call that raises the key's last line."""
+        dev = self.device
+        n, L = key.numel(), line_start.numel()
+        if line.numel() != n or tok.numel() != n:
+            raise ValueError("SpanTable.fold: line, key and tok differ in length")
+        if sig.numel() != L or eff.numel() != L:
+            raise ValueError("SpanTable.fold: sig and eff must have one entry per line")
+        for name, t, dt in (("line", line, torch.int32), ("key", key, torch.int64), ("tok", tok, torch.int32),
+                            ("sig", sig, torch.int64), ("eff", eff, torch.int64), ("text", text, torch.uint8),
+                            ("line_start", line_start, torch.int64)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError("SpanTable.fold: %s must be contiguous %s on %s" % (name, dt, dev))
+        if isinstance(line_base, bool) or not isinstance(line_base, int) or not 0 <= line_base < (1 << 62):
+            raise ValueError("SpanTable.fold: line_base must be an integer in [0, 2^62)")
+        if n == 0:
+            return
+        self._reserve(n)
+        pairs = (line.data_ptr(), key.data_ptr(), tok.data_ptr(), n, sig.data_ptr(), eff.data_ptr(), L, text.data_ptr(),
+                 text.numel(), line_start.data_ptr(), line_base)
+        tab, st = self._tab(), _s(self._key)
+        N.span_fold(tab, pairs, st, self._cuda)
+        N.span_ends(tab, pairs, st, self._cuda)
+
+    def purge(self, shift: int) -> int:
+        """Drop every span whose key is outside the hash sample ``shift``: the rows of the sample
+        (the filter is k_span_rows' own) into a fresh table of the same capacity -- the path of
+        growth. Returns the spans dropped."""
+        if not 0 <= shift <= 64:
+            raise ValueError("SpanTable.purge: shift must be 0..64")
+        used = self.used
+        if used == 0 or shift == 0:
+            return 0
+        rows = self._rows(used, shift)
+        kept = rows[0].numel()
+        if kept == used:
+            return 0
+        self._alloc(self.cap)
+        self._reinsert(rows, kept)
+        self._bound = kept
+        return used - kept
+
+
+# ---------------------------------------------------------------------------------------------
 # log timeline (csrc/kernels/timeline.hip): the timestamp of every line, counts per time bucket
 
-TS_NONE = -(1 << 63)        # a line without a stamp / without an effective time (csrc/kernels/ts_core.h)
+TS_NONE = -(1 << 63)       # a line without a stamp / without an effective time (csrc/kernels/ts_core.h)
 TL_TILE = 2048              # items (lines, then events) per block of k_tl_hist
 TL_LDS_SLOTS = 256          # buckets of its block table at most: more distinct buckets in a tile go to HBM directly
 

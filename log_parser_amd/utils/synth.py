@@ -446,6 +446,92 @@ def variant_log(n_lines: int, templates: List[str], seed: int = 0, rare_from: fl
                   "rareLines": rare, "rareRange": (lo, hi), "workers": 8}
 
 
+SPAN_HOST = "node0042x7"
+# (opening line, work lines, closing line) of a kind of span; %s: the id
+SPAN_KINDS = (
+    ("req", "INFO  [http] request %s started on route /api/orders",
+     ("DEBUG [db] query for %s took a while", "DEBUG [cache] lookup for %s missed"),
+     "INFO  [http] request %s completed with status ok"),
+    ("job", "INFO  [sched] job %s picked up by a worker",
+     ("DEBUG [sched] job %s made progress", "DEBUG [store] job %s wrote a checkpoint"),
+     "INFO  [sched] job %s finished"),
+    ("conn", "INFO  [net] connection %s accepted",
+     ("DEBUG [net] connection %s received a frame",),
+     "INFO  [net] connection %s closed by the peer"),
+)
+
+
+def span_log(n_lines: int, seed: int = 0, concurrency: int = 8, step_ms: int = 7, crlf_rate: float = 0.0) -> Tuple[str, dict]:
+    """A log of exactly ``n_lines`` (>= 64) lines of interleaved requests of three kinds
+    (``SPAN_KINDS``): every request has an id of its own -- ``req0000017``, ``job0000018``, ... --
+    on its opening line, its work lines and its closing line; up to ``concurrency`` are open at a
+    time, and all of them are closed before the log ends. The stamps advance ``step_ms`` per line
+    from ``TREND_T0_MS``. Planted: one ``req`` that opens and works like the others and never
+    closes (``unfinished``); one ``req`` that opens near the start and closes near the end
+    (``long``: far longer than the rest); the token ``SPAN_HOST`` on every line; about one line
+    in fifty is an unstamped continuation line that names the request of the line before it; about
+    one stamped line in two hundred carries the stamp of twenty lines before. Returns (text,
+    facts): ``long`` / ``unfinished`` (the ids), ``host``, ``ids`` (requests opened), ``kinds``."""
+    if n_lines < 64:
+        raise ValueError("span_log: n_lines must be at least 64")
+    rng = random.Random(seed)
+    serial = [0]
+
+    def new_id(kind: int) -> Tuple[int, str]:
+        serial[0] += 1
+        return kind, "%s%07d" % (SPAN_KINDS[kind][0], serial[0])
+
+    def stamp(i: int, back: bool) -> str:
+        ms = i * step_ms + 43200000 - (20 * step_ms if back else 0)
+        d, ms = divmod(ms, 86400000)
+        return "2025-09-%02dT%02d:%02d:%02d.%03dZ" % (19 + d % 10, ms // 3600000, ms // 60000 % 60, ms // 1000 % 60, ms % 1000)
+
+    out: List[str] = []
+
+    def emit(body: str) -> None:
+        out.append("%s %s host=%s" % (stamp(len(out), len(out) > 8 and rng.random() < 0.005), body, SPAN_HOST))
+
+    long_at, long_end, unf_at = max(2, n_lines // 50), n_lines - max(4, n_lines // 50), n_lines // 2
+    long_id = unf_id = None
+    unf_work = 0
+    active: List[Tuple[int, str]] = []
+    while len(out) < n_lines:
+        i, left = len(out), n_lines - len(out)
+        owe = len(active) + (long_id is not None and i <= long_end)     # closing lines still to come
+        if long_id is None and i >= long_at:
+            long_id = new_id(0)
+            emit(SPAN_KINDS[0][1] % long_id[1])
+        elif long_id is not None and i == long_end:
+            emit(SPAN_KINDS[0][3] % long_id[1])
+        elif left <= owe + 1 and active:
+            kind, sid = active.pop(rng.randrange(len(active)))
+            emit(SPAN_KINDS[kind][3] % sid)
+        elif unf_id is None and i >= unf_at:
+            unf_id = new_id(0)
+            emit(SPAN_KINDS[0][1] % unf_id[1])
+        elif unf_id is not None and unf_work < 3 and rng.random() < 0.2:
+            unf_work += 1
+            emit(SPAN_KINDS[0][2][unf_work % 2] % unf_id[1])
+        elif len(active) < concurrency and left > owe + 3 and (not active or rng.random() < 0.3):
+            active.append(new_id(rng.randrange(len(SPAN_KINDS))))
+            emit(SPAN_KINDS[active[-1][0]][1] % active[-1][1])
+        elif active:
+            k = rng.randrange(len(active))
+            kind, sid = active[k]
+            if rng.random() < 0.25:
+                active.pop(k)
+                emit(SPAN_KINDS[kind][3] % sid)
+            else:
+                emit(rng.choice(SPAN_KINDS[kind][2]) % sid)
+                if rng.random() < 0.02 and n_lines - len(out) > owe + 2:
+                    out.append("    ... still waiting on %s host=%s" % (sid, SPAN_HOST))
+        else:
+            emit("INFO  [main] idle tick")
+    text = "".join(line + ("\r\n" if rng.random() < crlf_rate else "\n") for line in out)
+    return text, {"long": long_id[1], "unfinished": unf_id[1], "host": SPAN_HOST, "ids": serial[0],
+                  "kinds": len(SPAN_KINDS)}
+
+
 TREND_T0_MS = 1758283200000        # 2025-09-19T12:00:00Z
 TREND_STOPPED = "INFO  [lease] heartbeat: renewed leader lease, sequence %d"
 TREND_STARTED = "ERROR [net] connection reset by peer while reading from upstream %d"
